@@ -10,6 +10,11 @@ gowalla-shaped synthetic graph (BASELINE.json configs[2]): device-side sampling 
 epoch stream (amortised: one launch per epoch, inside the timed region), LightGCN
 propagation forward (3 SpMM), BPR head, propagation backward (3 SpMM), dense TF-Adam.
 All inputs are resident in HBM before the timed region.  One JSON line on rank 0.
+
+A plain run does only what the headline needs: set up, warm up, time --steps steps, write
+--dump-outputs DIR if given, print the line.  --full adds every other measurement (whole
+timed epoch, rooflines, evaluation, the other BASELINE configs, CPU baselines, multi-rank
+extras) and the full line in bench_full.json.
 """
 import argparse
 import json
@@ -54,9 +59,19 @@ def parse():
                          "default: sliced — column slabs all-gathered under the one-launch SpMM of the previous slab, "
                          "exact; reduce — item rows as per-rank partials + all-to-all, 5x fewer bytes at config 4, "
                          "within fp32 rounding)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the whole timed epoch, the SpMM and evaluation rooflines, "
+                         "the evaluation, BPR-MF, NGCF / Mult-VAE, ml-100k and config-4 legs, the CPU baselines and "
+                         "the multi-rank extras (exchange, one-GPU and strong-scaling figures).  Without it a run "
+                         "sets up, warms up, times --steps steps, writes --dump-outputs and prints the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step left to its caller (the trained "
+                         "embedding tables, float32) as DIR/<name>.npy; at most 64 MB in all (a fixed, seeded sample "
+                         "of the rows beyond that)")
     ap.add_argument("--full-line", action="store_true",
-                    help="print the full line (every leg with kernels, notes and samples) instead of the compact one the "
-                         "driver parses; the full line always goes to bench_full.json as well")
+                    help="with --full: print the full line (every leg with kernels, notes and samples) instead of the "
+                         "compact one the driver parses; a --full run always writes the full line to bench_full.json")
+    # the --no-* switches below trim the --full run; a plain run has none of these legs
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-steps", type=int, default=24)
     ap.add_argument("--eval-mode", choices=("pruned", "materialised"), default="pruned")
@@ -73,6 +88,26 @@ def parse():
                     help="fraction of BASELINE configs[3] (10^7 users, 10^6 items, 2*10^8 interactions) the one-GPU "
                          "leg runs at on this one GPU; 1.0 is the full size (213 ms/step)")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 60 << 20          # under 64 MB with the .npy headers
+
+
+def dump_outputs(out_dir, tables):
+    """Write the device tensors of `tables` ({name: 2-D tensor}) as out_dir/<name>.npy in float32.  Past
+    DUMP_LIMIT_BYTES in all, every table keeps the same fraction of its rows: a sorted sample drawn with a fixed
+    seed, so that two runs with the same arguments write the same rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(t.numel() * 4 for t in tables.values())
+    keep = min(1.0, DUMP_LIMIT_BYTES / max(total, 1))
+    for k, (name, t) in enumerate(sorted(tables.items())):
+        n = t.shape[0]
+        if keep < 1.0:
+            m = max(1, int(n * keep))
+            rows = np.sort(np.random.RandomState(1234 + k).choice(n, m, replace=False))
+            import torch
+            t = t.index_select(0, torch.from_numpy(rows).to(t.device))
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
 
 
 def spawn_ranks(n):
@@ -268,6 +303,65 @@ def main():
                     "batch_plan_launches": (sampler.epoch - epochs_before) if sampler.plans else
                     ("one per step (sorted inside the step)" if not rowshard else 0)}
     triplets_per_s = comm.world * args.steps * args.batch / dt
+    if args.dump_outputs:
+        # what the last timed step handed back to its caller: the embedding tables it updated in place
+        if rowshard:
+            tables = {"E0_rank%d" % comm.rank: lg.E0.reshape(-1, lg.E0.shape[-1])}   # this rank's slabs as they lie
+        else:
+            t = lg.table() if colshard else lg.E0[:, :lg.d_real]                   # colshard: this rank's columns
+            tables = {"user_embeddings": t[:U], "item_embeddings": t[U:]}
+        if comm.rank == 0:
+            dump_outputs(args.dump_outputs, tables)
+        del tables
+    head = {
+        "metric": "BPR triplets/sec (LightGCN-%s)" % args.shape, "value": triplets_per_s,
+        "unit": "triplets/s", "n_gpus": comm.world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "data_note": "train interactions are a synthetic twin of the named shape (neurec_amd/synth.py: gowalla.train is "
+                     "absent from the reference tree); test split: %s" % (data_test if not config4 else "none"),
+        "config": {"workload": "LightGCN on synthetic %s-shaped interactions (U=%d, I=%d, E=%d), "
+                               "%d layers, dim %d, B=%d per GPU, adj=pre, Adam lr=0.01 reg=1e-3"
+                               % (args.shape, U, I, train_nnz, args.layers, args.dim, args.batch),
+                   "global_batch": comm.world * args.batch,
+                   "parallelism": (
+                       "colshard%d (every rank holds %d of the %d embedding columns for all nodes and steps on the global "
+                       "batch of %d; one all-gather of the per-triplet partial inner products per step: %d B)"
+                       % (comm.world, args.dim // comm.world, args.dim, global_batch, 12 * global_batch * comm.world)
+                       if colshard else
+                       "dp%d (replicated tables; every rank generates the same global epoch stream from the shared seed "
+                       "and steps on the global batch of %d: no exchange in training, tables bit-identical on all ranks)"
+                       % (comm.world, global_batch) if replicated else
+                       "dp%d (replicated tables; per step one all-gather of 12 B/triplet of ids, every rank steps on "
+                       "the global batch)" % comm.world if exchange else
+                       "rowshard%d (tables row-sharded; %s hop, all-to-all row lookups, owner-local Adam)"
+                       % (comm.world, lg.hop) if rowshard else
+                       "dp%d (replicated tables, one all-reduce of dL/dE0 per step)" % comm.world)
+                   if comm.active else "single GPU"},
+    }
+    if comm.active:
+        import torch.distributed as dist
+        head["rccl_ranks"] = comm.world if dist.get_backend() == "nccl" else 0
+        head["dist_backend"] = dist.get_backend()
+        # what of the step is partitioned over the ranks and what every rank repeats (VERDICT r2 #2)
+        head["redundant_compute"] = {
+            "replicated": "everything: every rank runs the whole step on the global batch (no exchange)",
+            "triplets": "everything but the sampler: ids are exchanged, every rank runs the whole step",
+            "allreduce": "the propagation's full hops (batch-independent) are repeated on every rank; sampler, BPR "
+                         "head and the batch-masked hops are partitioned (each rank its B triplets)",
+            "rowshard": False,
+            "colshard": False}[args.dp_mode]
+        if colshard:
+            head["redundant_compute_note"] = ("nothing is computed twice: a rank gathers 1/N of every row's bytes; only the "
+                                              "CSR indices (8 B per non-zero) are read by every rank")
+    if not args.full:
+        # a plain run: the headline and nothing else (every other leg, roofline and baseline is --full's)
+        if exchange:
+            comm.allgather_cat_finish(inflight[0])       # drain the prefetched id gather
+        if comm.rank == 0:
+            print(json.dumps(dict(head, timed_region=timed_region)))
+        comm.shutdown()
+        return
     run_steps(1, loss2)                                  # untimed: loss of one more step, for the record
     # ONE WHOLE EPOCH, timed (the metric is E / epoch wall time, sampler included): the
     # sampler's launch, the batch plans and EVERY batch of the permuted stream, the short last one too
@@ -592,31 +686,7 @@ def main():
                         "rescoring is bucketed by tile, so an item tile is read once per 32 users (r03: once per user, "
                         "5.6 GB through the L2s, 0.43 ms); the phase is a chain of six short launches" % (tiles, n_keep)}
 
-    line = {
-        "metric": "BPR triplets/sec (LightGCN-%s)" % args.shape, "value": triplets_per_s,
-        "unit": "triplets/s", "n_gpus": comm.world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "data_note": "train interactions are a synthetic twin of the named shape (neurec_amd/synth.py: gowalla.train is "
-                     "absent from the reference tree); test split: %s" % (data_test if not config4 else "none"),
-        "config": {"workload": "LightGCN on synthetic %s-shaped interactions (U=%d, I=%d, E=%d), "
-                               "%d layers, dim %d, B=%d per GPU, adj=pre, Adam lr=0.01 reg=1e-3"
-                               % (args.shape, U, I, train_nnz, args.layers, args.dim, args.batch),
-                   "global_batch": comm.world * args.batch,
-                   "parallelism": (
-                       "colshard%d (every rank holds %d of the %d embedding columns for all nodes and steps on the global "
-                       "batch of %d; one all-gather of the per-triplet partial inner products per step: %d B)"
-                       % (comm.world, args.dim // comm.world, args.dim, global_batch, 12 * global_batch * comm.world)
-                       if colshard else
-                       "dp%d (replicated tables; every rank generates the same global epoch stream from the shared seed "
-                       "and steps on the global batch of %d: no exchange in training, tables bit-identical on all ranks)"
-                       % (comm.world, global_batch) if replicated else
-                       "dp%d (replicated tables; per step one all-gather of 12 B/triplet of ids, every rank steps on "
-                       "the global batch)" % comm.world if exchange else
-                       "rowshard%d (tables row-sharded; %s hop, all-to-all row lookups, owner-local Adam)"
-                       % (comm.world, lg.hop) if rowshard else
-                       "dp%d (replicated tables, one all-reduce of dL/dE0 per step)" % comm.world)
-                   if comm.active else "single GPU"},
+    line = dict(head, **{
         "final_loss": [float(x) for x in loss2.cpu().numpy()], "timed_region": timed_region,
         "epoch_timed": epoch_timed,
         "epoch_amortised": {"value": epoch_amortised, "unit": "triplets/s",
@@ -625,7 +695,7 @@ def main():
                                     "definition of the metric" % (steps_per_epoch, epoch_ms)},
         "eval": eval_info, "mf": mf_info, "roofline": roofline,
         "device": E.device_info(),
-    }
+    })
     if config4 and config4_eval:
         try:
             ev4 = _config4_eval(full, comm, trc, I, args.dim, dev, 65536, batch_rows=args.config4_eval_batch)
@@ -652,21 +722,6 @@ def main():
                                      "share_of_step": ex_ms / (dt / args.steps * 1e3),
                                      "note": "inside the timed step already; gloo stages through the host (two ranks on "
                                              "one GPU in the tests): only backend nccl is the xGMI figure"}
-    if comm.active:
-        import torch.distributed as dist
-        line["rccl_ranks"] = comm.world if dist.get_backend() == "nccl" else 0
-        line["dist_backend"] = dist.get_backend()
-        # what of the step is partitioned over the ranks and what every rank repeats (VERDICT r2 #2)
-        line["redundant_compute"] = {
-            "replicated": "everything: every rank runs the whole step on the global batch (no exchange)",
-            "triplets": "everything but the sampler: ids are exchanged, every rank runs the whole step",
-            "allreduce": "the propagation's full hops (batch-independent) are repeated on every rank; sampler, BPR "
-                         "head and the batch-masked hops are partitioned (each rank its B triplets)",
-            "rowshard": False,
-            "colshard": False}[args.dp_mode]
-        if colshard:
-            line["redundant_compute_note"] = ("nothing is computed twice: a rank gathers 1/N of every row's bytes; only the "
-                                              "CSR indices (8 B per non-zero) are read by every rank")
     if comm.rank == 0 and comm.world == 1 and default_workload and not args.no_eval:
         # ONE rank's share of a W-rank column-sharded job, measured on this GPU (neurec_amd/colshard.py): rank 0's dim/W
         # columns, the global batch of W*B — what every rank of the job computes per step; the job adds ONE all-gather

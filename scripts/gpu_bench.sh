@@ -1,6 +1,7 @@
 #!/bin/bash
 # usage (through gpurun): bash scripts/gpu_bench.sh <tag> [bench.py args...]  -> gpurun_out/r03/<tag>.json
 tag=$1; shift
+set -- --full "$@"     # the summary below reads the legs of the --full line
 mkdir -p gpurun_out/r03
 python bench.py "$@" > gpurun_out/r03/$tag.json 2> gpurun_out/r03/$tag.err
 echo "rc=$?"; tail -c 1500 gpurun_out/r03/$tag.err

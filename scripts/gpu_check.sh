@@ -24,11 +24,11 @@ for ph in $PHASES; do
       timeout 600 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -30 | tee -a "$OUT/summary.txt" ;;
     bench)
       echo "== bench" | tee -a "$OUT/summary.txt"
-      timeout 420 python bench.py --gpus 1 --steps 300 --warmup 30 ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err"
+      timeout 420 python bench.py --gpus 1 --steps 300 --warmup 30 --full ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err"
       tail -5 "$OUT/bench.err" | tee -a "$OUT/summary.txt"; cat "$OUT/bench.json" | tee -a "$OUT/summary.txt" ;;
     prof)
       echo "== rocprofv3 kernel stats" | tee -a "$OUT/summary.txt"
-      ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OLDPWD/$OUT/prof" -o bench -- python "$OLDPWD/bench.py" --gpus 1 --steps 100 --warmup 10 --no-cpu-baseline > "$OLDPWD/$OUT/prof_bench.json" 2> "$OLDPWD/$OUT/prof.err" )
+      ( cd "$TMPDIR" && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OLDPWD/$OUT/prof" -o bench -- python "$OLDPWD/bench.py" --gpus 1 --steps 100 --warmup 10 --full --no-cpu-baseline > "$OLDPWD/$OUT/prof_bench.json" 2> "$OLDPWD/$OUT/prof.err" )
       find "$OUT/prof" -name "*kernel_stats*" | head -3 | tee -a "$OUT/summary.txt"
       f=$(find "$OUT/prof" -name "*kernel_stats.csv" | head -1)
       [ -n "$f" ] && head -25 "$f" | tee -a "$OUT/summary.txt"

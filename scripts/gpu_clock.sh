@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp
 OUT=gpurun_out/clock
 mkdir -p "$OUT"
-( cd /tmp && timeout 300 rocprofv3 --pmc GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d "$OLDPWD/$OUT/run" -o b -- python "$OLDPWD/bench.py" --gpus 1 --steps 20 --warmup 2 --no-cpu-baseline --no-mf > /dev/null 2> "$OLDPWD/$OUT/err.txt" )
+( cd "$TMPDIR" && timeout 300 rocprofv3 --pmc GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d "$OLDPWD/$OUT/run" -o b -- python "$OLDPWD/bench.py" --gpus 1 --steps 20 --warmup 2 --full --no-cpu-baseline --no-mf > /dev/null 2> "$OLDPWD/$OUT/err.txt" )
 c=$(find "$OUT/run" -name "*counter_collection.csv" | head -1)
 [ -z "$c" ] && { tail -5 "$OUT/err.txt"; exit 1; }
 python - "$c" <<'PY'

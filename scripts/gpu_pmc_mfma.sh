@@ -9,7 +9,7 @@ i=0
 while read -r group; do
   [ -z "$group" ] && continue
   i=$((i+1))
-  ( cd /tmp && timeout 200 rocprofv3 --pmc $group --kernel-trace --output-format csv -d "$OLDPWD/$OUT/g$i" -o b -- python "$OLDPWD/bench.py" --gpus 1 --steps 3 --warmup 1 --no-cpu-baseline --no-mf > /dev/null 2> "$OLDPWD/$OUT/g$i.err" )
+  ( cd "$TMPDIR" && timeout 200 rocprofv3 --pmc $group --kernel-trace --output-format csv -d "$OLDPWD/$OUT/g$i" -o b -- python "$OLDPWD/bench.py" --gpus 1 --steps 3 --warmup 1 --full --no-cpu-baseline --no-mf > /dev/null 2> "$OLDPWD/$OUT/g$i.err" )
   f=$(find "$OUT/g$i" -name "*counter_collection.csv" | head -1)
   echo "== $group"
   if [ -n "$f" ]; then python - "$f" <<'PY'

@@ -9,10 +9,10 @@ C4SCALE=0.25 bash scripts/gpu_pmc.sh 2>&1 | tail -12
 cp gpurun_out/pmc/pmc_traffic.json $OUT/pmc_traffic.json
 cp gpurun_out/pmc/pmc_traffic.json profiles/r05_pmc_traffic.json
 echo "== bench (plain)"
-NEUREC_BENCH_FULL=$OUT/final_bench_full.json timeout 900 python bench.py > $OUT/final_bench.json 2> $OUT/final_bench.err
+NEUREC_BENCH_FULL=$OUT/final_bench_full.json timeout 900 python bench.py --full > $OUT/final_bench.json 2> $OUT/final_bench.err
 tail -2 $OUT/final_bench.err; head -c 600 $OUT/final_bench.json; echo
 echo "== rocprofv3 kernel stats of the bench command"
-( cd /tmp && NEUREC_BENCH_FULL=/tmp/prof_full.json timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OLDPWD/$OUT/prof" -o bench -- python "$OLDPWD/bench.py" --steps 100 --warmup 10 --no-cpu-baseline > "$OLDPWD/$OUT/prof_bench.json" 2> "$OLDPWD/$OUT/prof.err" )
+( cd "$TMPDIR" && NEUREC_BENCH_FULL="$TMPDIR/prof_full.json" timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OLDPWD/$OUT/prof" -o bench -- python "$OLDPWD/bench.py" --steps 100 --warmup 10 --full --no-cpu-baseline > "$OLDPWD/$OUT/prof_bench.json" 2> "$OLDPWD/$OUT/prof.err" )
 f=$(find "$OUT/prof" -name "*kernel_stats.csv" | head -1)
 [ -n "$f" ] && cp "$f" $OUT/bench_kernel_stats.csv && head -12 "$f" | cut -c1-160
 find "$OUT/prof" -name "*kernel_trace.csv" -delete

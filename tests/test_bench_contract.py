@@ -79,7 +79,7 @@ def test_bench_metric_is_the_north_star_metric():
 def test_bench_cli_has_the_contract_flags_and_safe_defaults():
     with open(os.path.join(ROOT, "bench.py")) as f:
         src = f.read()
-    for flag in ("--gpus", "--steps", "--warmup"):
+    for flag in ("--gpus", "--steps", "--warmup", "--full", "--dump-outputs"):
         assert re.search(r'add_argument\(\s*"%s"' % flag, src), flag
     m = re.search(r'add_argument\(\s*"--gpus"[^)]*default=(\d+)', src)
     assert m and int(m.group(1)) == 1

@@ -18,7 +18,7 @@ def _run(mode, port):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--steps", "6", "--warmup", "2", "--scale", "0.05", "--batch", "256",
-           "--no-cpu-baseline", "--no-mf", "--config4-scale", "0.002", "--full-line"] + (["--dp-mode", mode] if mode else [])
+           "--no-cpu-baseline", "--no-mf", "--config4-scale", "0.002", "--full", "--full-line"] + (["--dp-mode", mode] if mode else [])
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=280)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -72,7 +72,7 @@ def test_one_rank_bench_line(extra):
     """The default single-process line (training + evaluation + BPR-MF legs) and the config-4 path
     (device-generated graph, row-sharded engine) on small shapes: contract fields present and finite."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2",
-           "--no-cpu-baseline", "--full-line"] + extra
+           "--no-cpu-baseline", "--full", "--full-line"] + extra
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=280)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -91,13 +91,12 @@ def test_one_rank_bench_line(extra):
         assert d["eval"]["users_per_sec"] > 0 and d["eval"]["n_users"] > 0       # config 4 has an evaluation leg (r06)
 
 
-def test_default_line_is_the_compact_one():
+def test_default_line_is_the_compact_one(tmp_path):
     """Without --full-line the printed line is the compact form the driver's parser keeps whole: the
     contract keys, `roofline` with the secondary legs as flat numbers, no prose; the full line goes to a file."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2",
-           "--no-cpu-baseline", "--scale", "0.05", "--batch", "256", "--no-config4", "--no-config5"]
-    full = os.path.join(ROOT, "gpurun_out", "test_full_line.json")
-    os.makedirs(os.path.dirname(full), exist_ok=True)
+           "--no-cpu-baseline", "--scale", "0.05", "--batch", "256", "--no-config4", "--no-config5", "--full"]
+    full = str(tmp_path / "test_full_line.json")
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=280, env=dict(os.environ, NEUREC_BENCH_FULL=full))
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -120,7 +119,7 @@ def test_plain_shell_launch_starts_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(NEUREC_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--scale", "0.05",
-           "--batch", "256", "--no-cpu-baseline", "--no-mf", "--no-config4", "--no-config5", "--full-line"]
+           "--batch", "256", "--no-cpu-baseline", "--no-mf", "--no-config4", "--no-config5", "--full", "--full-line"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=280)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -128,3 +127,32 @@ def test_plain_shell_launch_starts_its_own_ranks():
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["dist_backend"] == "gloo" and d["config"]["global_batch"] == 512
     assert d["strong_scaling"]["global_batch"] == 256 and d["value"] > 0
+
+
+def test_plain_line_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and prints the headline alone; --dump-outputs writes the
+    tables the last timed step updated, float32, the same bytes for the same arguments."""
+    def run(out):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+               "--scale", "0.05", "--batch", "256", "--dump-outputs", str(out)]
+        r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=280)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        return json.loads(lines[0])
+    d = run(tmp_path / "a")
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert k in d, k
+    assert d["unit"] == "triplets/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == 7 and d["timed_region"]["steps"] == 7
+    assert abs(d["value"] - 256 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    for k in ("roofline", "eval", "mf", "epoch_timed", "cpu_baseline", "final_loss"):
+        assert k not in d, k                                           # the other legs are --full's
+    run(tmp_path / "b")
+    import numpy as np
+    names = sorted(os.listdir(str(tmp_path / "a")))
+    assert names == ["item_embeddings.npy", "user_embeddings.npy"]
+    for n in names:
+        a, b = np.load(str(tmp_path / "a" / n)), np.load(str(tmp_path / "b" / n))
+        assert a.dtype == np.float32 and a.shape[1] == 64 and np.isfinite(a).all()
+        assert np.array_equal(a, b), n

@@ -49,26 +49,41 @@ def test_configurator_coercion_and_precedence(tmp_path):
     assert "NeuRec hyperparameters:" in str(conf) and "LightGCN's hyperparameters:" in str(conf)
 
 
-@pytest.mark.skipif(not has_ref, reason="/root/reference not present")
 def test_configurator_reads_unchanged_reference_files_like_the_reference():
-    ref_mod = _load_ref_module("util/configurator.py", "ref_configurator")
+    """the reference's NeuRec.properties + conf/<Model>.properties (tests/golden/neurec_conf/) read as the reference's
+    own Configurator read them (tests/golden/configurator_reference.json, make_configurator_fixture.py); where
+    the reference tree is present, against its live Configurator and files as well"""
+    import json
+    from conftest import GOLDEN
+    with open(os.path.join(GOLDEN, "configurator_reference.json")) as f:
+        recorded = json.load(f)
+    ref_mod = _load_ref_module("util/configurator.py", "ref_configurator") if has_ref else None
     cwd, argv = os.getcwd(), sys.argv
-    os.chdir(REF)
-    try:
-        for model in ("MF", "LightGCN", "NGCF", "MultiVAE"):
-            sys.argv = ["main.py", "--recommender=%s" % model, "--num_thread=4"]
-            theirs = ref_mod.Configurator("NeuRec.properties", default_section="hyperparameters")
-            ours = Configurator("NeuRec.properties", default_section="hyperparameters",
-                                argv=sys.argv[1:])
-            keys = list(theirs.lib_arg) + list(theirs.alg_arg)
-            assert keys == list(ours.lib_arg) + list(ours.alg_arg)
-            for k in keys:
-                assert ours[k] == theirs[k] and type(ours[k]) is type(theirs[k]), k
-            assert ours.params_str() == theirs.params_str()
-            assert str(ours) == str(theirs)
-    finally:
-        os.chdir(cwd)
-        sys.argv = argv
+    for where in [os.path.join(GOLDEN, "neurec_conf")] + ([REF] if has_ref else []):
+        os.chdir(where)
+        try:
+            for model in ("MF", "LightGCN", "NGCF", "MultiVAE"):
+                sys.argv = ["main.py", "--recommender=%s" % model, "--num_thread=4"]
+                ours = Configurator("NeuRec.properties", default_section="hyperparameters",
+                                    argv=sys.argv[1:])
+                want = recorded[model]
+                assert want["keys"] == list(ours.lib_arg) + list(ours.alg_arg)
+                for k in want["keys"]:
+                    assert [type(ours[k]).__name__, repr(ours[k])] == want["values"][k], k
+                assert ours.params_str() == want["params_str"]
+                assert str(ours) == want["str"]
+                if ref_mod is None:
+                    continue
+                theirs = ref_mod.Configurator("NeuRec.properties", default_section="hyperparameters")
+                keys = list(theirs.lib_arg) + list(theirs.alg_arg)
+                assert keys == list(ours.lib_arg) + list(ours.alg_arg)
+                for k in keys:
+                    assert ours[k] == theirs[k] and type(ours[k]) is type(theirs[k]), k
+                assert ours.params_str() == theirs.params_str()
+                assert str(ours) == str(theirs)
+        finally:
+            os.chdir(cwd)
+            sys.argv = argv
 
 
 # ------------------------------------------------------------------ DataIterator
@@ -158,12 +173,23 @@ def test_dataset_split_cache_and_views(tmp_path):
         assert not set(v) & set(ds3.train_matrix[u].indices) and not set(v) & set(ds3.test_matrix[u].indices)
 
 
-@pytest.mark.skipif(not os.path.isfile(os.path.join(REF, "dataset", "ml-100k.rating")),
-                    reason="real ml-100k only exists in the reference tree")
 def test_dataset_on_real_ml100k_matches_survey_counts(tmp_path):
+    """the reference's dataset/ml-100k.rating, written back from tests/golden/ml100k_rating.npz"""
+    from conftest import GOLDEN
     from neurec_amd.data import Dataset
+    spec = importlib.util.spec_from_file_location("make_ml100k_rating_fixture",
+                                                  os.path.join(GOLDEN, "make_ml100k_rating_fixture.py"))
+    mk = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mk)
+    data_dir = tmp_path / "dataset"
+    data_dir.mkdir()
+    rating = mk.write_rating_file(str(data_dir / "ml-100k.rating"))
+    src = os.path.join(REF, "dataset", "ml-100k.rating")
+    if os.path.isfile(src):                                   # the fixture IS the file (build container only)
+        with open(src, "rb") as f, open(rating, "rb") as g:
+            assert f.read() == g.read()
     path = defaults.write_default_configs(str(tmp_path), overrides={
-        "data.input.path": os.path.join(REF, "dataset"), "data.cache.path": str(tmp_path)})
+        "data.input.path": str(data_dir), "data.cache.path": str(tmp_path)})
     np.random.seed(2018)
     ds = Dataset(Configurator(path, default_section="hyperparameters", argv=[]))
     assert (ds.num_users, ds.num_items) == (943, 1682)

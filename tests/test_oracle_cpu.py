@@ -2,6 +2,8 @@
 reference's own compiled evaluator/sampler (tests/golden/make_golden.py), the
 known-answer vectors of SURVEY.md, and — when oracle/_ref is present — the
 reference code itself on fresh random inputs."""
+import os
+
 import numpy as np
 import pytest
 
@@ -58,22 +60,27 @@ def test_sampler_oracle_argument_errors():
         native.batch_randint_choice(10, [1, 2], exclusion=[[1]])
 
 
-@pytest.mark.skipif(not ref.available(), reason="oracle/_ref not built (no /root/reference)")
 def test_oracle_equals_live_reference_on_fresh_inputs():
-    rng = np.random.RandomState(7)
-    for trial in range(12):
-        rows, cols = 40, int(rng.randint(60, 2500))
-        k = int(rng.randint(1, min(60, cols // 2)))
-        s = rng.randn(rows, cols).astype(np.float32)
-        if trial % 3 == 1:
-            s = (np.round(s * 3) / 3).astype(np.float32)
-        if trial % 3 == 2:
-            s[rng.rand(rows, cols) < 0.3] = -np.inf
-        truth = [np.sort(rng.choice(cols, rng.randint(1, 30), replace=False)).tolist()
-                 for _ in range(rows)]
-        np.testing.assert_array_equal(native.eval_matrix(s, truth, [1, 2, 3, 4, 5], k),
-                                      ref.eval_matrix(s, truth, [1, 2, 3, 4, 5], k))
-        np.testing.assert_array_equal(native.arg_topk(s, k), ref.arg_topk(s, k))
+    """seeded inputs (tests/golden/make_golden_fresh_inputs.py) against the reference's results recorded for them
+    (tests/golden/ref_fresh_inputs.npz), and against the live reference where oracle/_ref is built"""
+    import importlib.util
+    from conftest import GOLDEN
+    spec = importlib.util.spec_from_file_location("make_golden_fresh_inputs",
+                                                  os.path.join(GOLDEN, "make_golden_fresh_inputs.py"))
+    mk = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mk)
+    want = np.load(os.path.join(GOLDEN, "ref_fresh_inputs.npz"))
+    n = 0
+    for trial, (s, truth, k) in enumerate(mk.fresh_inputs()):
+        got_eval = native.eval_matrix(s.copy(), truth, [1, 2, 3, 4, 5], k)
+        got_topk = native.arg_topk(s.copy(), k)
+        np.testing.assert_array_equal(got_eval, want["eval_%d" % trial])
+        np.testing.assert_array_equal(got_topk, want["topk_%d" % trial])
+        if ref.available():
+            np.testing.assert_array_equal(got_eval, ref.eval_matrix(s.copy(), truth, [1, 2, 3, 4, 5], k))
+            np.testing.assert_array_equal(got_topk, ref.arg_topk(s.copy(), k))
+        n += 1
+    assert n == 12 and len(want.files) == 24
 
 
 def test_score_chain_close_to_blas():
@@ -181,27 +188,35 @@ def test_torch_cpu_step_port_tracks_the_numpy_oracle():
     assert np.abs(t.E.numpy() - e).max() < 1e-4
 
 
-@pytest.mark.skipif(not __import__("oracle.ref", fromlist=["x"]).sampler_module(),
-                    reason="oracle/_ref (reference sampler modules) not built")
 def test_reference_sampler_module_runs_an_epoch():
     """oracle.ref.sampler_module() = the reference's data/sampler.py compiled unchanged: one epoch
     has the structure SURVEY Appendix A records (aligned triplets, negatives outside the user's
-    train items, last short batch kept)."""
+    train items, last short batch kept).  The epoch is the one recorded from it
+    (tests/golden/ref_sampler_epoch.json, make_ref_sampler_epoch.py); where oracle/_ref is built, the
+    live module's epoch must have the same structure."""
+    import importlib.util
+    import json
+    from conftest import GOLDEN
     from oracle import ref
+    spec = importlib.util.spec_from_file_location("make_ref_sampler_epoch",
+                                                  os.path.join(GOLDEN, "make_ref_sampler_epoch.py"))
+    mk = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mk)
+    with open(os.path.join(GOLDEN, "ref_sampler_epoch.json")) as f:
+        rec = json.load(f)
+    n, batches = rec["len"], rec["batches"]
+    epochs = [(n, batches)]
     mod = ref.sampler_module()
-    d = {0: [1, 3], 2: [0], 5: [2, 4, 6, 7]}
-
-    class DS:
-        num_items = 10
-
-        @staticmethod
-        def get_user_train_dict():
-            return d
-    s = mod.PairwiseSampler(DS, neg_num=1, batch_size=4, shuffle=False)
-    batches = list(s)
-    assert len(s) == 2 and [len(b[0]) for b in batches] == [4, 3]
-    users = sum((b[0] for b in batches), [])
-    pos = sum((b[1] for b in batches), [])
-    neg = sum((b[2] for b in batches), [])
-    assert users == [0, 0, 2, 5, 5, 5, 5] and pos == [1, 3, 0, 2, 4, 6, 7]
-    assert all(n not in d[u] and 0 <= n < 10 for u, n in zip(users, neg))
+    if mod is not None:
+        # the live epoch: its negatives come from libc rand(), whose state other tests of the process may have moved
+        live = mk.epoch(mod)
+        assert live[0] == n and [b[:2] for b in live[1]] == [b[:2] for b in batches]
+        epochs.append(live)
+    d = mk.TRAIN
+    for n, batches in epochs:
+        assert n == 2 and [len(b[0]) for b in batches] == [4, 3]
+        users = sum((b[0] for b in batches), [])
+        pos = sum((b[1] for b in batches), [])
+        neg = sum((b[2] for b in batches), [])
+        assert users == [0, 0, 2, 5, 5, 5, 5] and pos == [1, 3, 0, 2, 4, 6, 7]
+        assert all(n not in d[u] and 0 <= n < 10 for u, n in zip(users, neg))
