@@ -348,8 +348,6 @@ class ScoreGemmWide:
     tables read as they lie — the same k-ascending fmaf chain per score.  The evaluation then takes the materialised
     path (score slab -> train mask -> select); there is no tile-maxima form at these widths."""
 
-    wide = True
-
     def __init__(self, item_table, max_rows):
         self.cols, self.d = item_table.shape
         self.max_rows = int(max_rows)
@@ -459,6 +457,14 @@ def eval_tiles(M, user_table, gemm, users, train_csr, truth_csr, metric_ids, top
     return out
 
 
+# What the scoring engine's item side (ScoreGemm's workspace) holds against the table being evaluated, in the codes
+# of the native calls: ITEMS_CURRENT this table's copies; ITEMS_STALE the previous table's; ITEMS_OPERAND_STALE this
+# table's except the fp32 scoring loop's operand copy.  nrhip_eval_redo's reload_items takes the state and reloads
+# what is stale; nrhip_eval_pruned's prepare_items takes ITEMS_STALE to load all of it or, with a filter,
+# ITEMS_OPERAND_STALE to load all but the operand copy (nothing in that call reads it), and leaves it in that state.
+ITEMS_CURRENT, ITEMS_STALE, ITEMS_OPERAND_STALE = 0, 1, 2
+
+
 class PrunedEvaluation:
     """nrhip_eval_pruned: the pruned evaluation of a whole user list in one native call (tile search, planned train
     strikes, fp32 rescoring + ranking + certificate + metrics per batch, then the column sums and the flagged-row
@@ -467,7 +473,7 @@ class PrunedEvaluation:
     certificate failed)."""
 
     def __init__(self, gemm, filt, plan, train_csr, truth_csr, metric_ids, top_k, n_keep, batch_rows):
-        from ._lib import EvalPrunedArgs
+        from ._lib import EvalPrunedArgs, EvalRedoArgs
         self.gemm, self.filt, self.plan = gemm, filt, plan
         self.train, self.truth = train_csr, truth_csr
         self.top_k, self.n_keep, self.batch_rows = int(top_k), int(n_keep), int(batch_rows)
@@ -482,54 +488,55 @@ class PrunedEvaluation:
         call("nrhip_eval_tiles_bounded_workspace_bytes", self.batch_rows, gemm.cols, self.top_k, self.n_keep, C.byref(nb))
         self.tiles_ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
         self.sums = torch.empty(self.nm * self.top_k + 2, dtype=torch.float64, device=dev)
-        self.cs_ws = None
-        self.args = EvalPrunedArgs()
+        self.cs_ws, self._cs_n = None, None                   # the column sums' workspace, sized for _cs_n rows
+        self.args, self._last = EvalPrunedArgs(), None        # the argument block and the key of the tensors it holds
+        self._item_copy = None                                # a contiguous copy of the item table the block points at
+        self._redo_args = EvalRedoArgs()
+        self._redo_count = torch.empty(1, dtype=torch.int32, device=dev)      # (zeroed inside nrhip_eval_redo)
+        self._redo_rows = self._redo_fixed = self._redo_ws = None
 
-    def run(self, user_table, item_table, users, row_of, per_user, flags, prepare_items=True):
+    def run(self, user_table, item_table, users, row_of, per_user, flags, prepare_items=ITEMS_STALE):
         a, g, f, pl = self.args, self.gemm, self.filt, self.plan
         n = users.numel()
         # the argument block of the previous call stands when the six tensors lie where they lay (the block holds nothing
         # of them but pointers, strides and counts; everything else in it belongs to this object): an evaluation per
         # epoch hands over the same tables, user list and buffers every time, and filling ~40 fields costs more than a
         # small launch
-        key = (user_table.data_ptr(), user_table.stride(0), item_table.data_ptr(), item_table.stride(0), item_table.stride(1),
-               users.data_ptr(), n, row_of.data_ptr(), per_user.data_ptr(), flags.data_ptr(), user_table.dtype,
-               item_table.dtype, users.dtype, per_user.dtype, flags.dtype, row_of.dtype, user_table.stride(1),
-               per_user.is_contiguous())
-        if getattr(self, "_last", None) == key:
-            a.prepare_items = int(prepare_items)
-            call("nrhip_eval_pruned", C.byref(a), _stream())
-            return per_user, flags, self.sums
-        if getattr(self, "_cs_n", None) != n:
-            nb = C.c_size_t(0)
-            call("nrhip_colsum_workspace_bytes", max(n, 1), self.nm * self.top_k, C.byref(nb))
-            if self.cs_ws is None or self.cs_ws.numel() < nb.value:
-                self.cs_ws = torch.empty(max(nb.value, 256), dtype=torch.uint8, device=g.ws.device)
-            self._cs_n = n
-        if item_table.stride(1) != 1:
-            item_table = item_table.contiguous()
-            key = None                                       # (a temporary copy: nothing to remember)
-        ptr = lambda t: t.data_ptr()
-        a.P, a.ldp, a.Q, a.ldq, a.d, a.cols = ptr(user_table), user_table.stride(0), ptr(item_table), item_table.stride(0), g.d, g.cols
-        a.users, a.n_users, a.batch_rows = ptr(users), n, self.batch_rows
-        a.tr_indptr, a.tr_indices = ptr(self.train.indptr), ptr(self.train.indices)
-        a.truth_indptr, a.truth_indices = ptr(self.truth.indptr), ptr(self.truth.indices)
-        a.chunk_tile, a.chunk_begin, a.n_chunks = ptr(pl.chunk_tile), ptr(pl.chunk_begin), pl.n_chunks
-        a.tile_ptr, a.plan_user, a.plan_mask, a.row_of = ptr(pl.tile_ptr), ptr(pl.user), ptr(pl.mask), ptr(row_of)
-        a.metric_ids, a.n_metric, a.top_k, a.n_keep = self.ids, self.nm, self.top_k, self.n_keep
-        # prepare_items: False / True, or 2 = the item side without the fp32 scoring loop's operand copy (filter only)
-        a.use_filter, a.prepare_items = (f.use_filter if f is not None else 0), int(prepare_items)
-        a.gemm_ws, a.gemm_ws_bytes = ptr(g.ws), g.ws.numel()
-        a.filter_ws, a.filter_ws_bytes = (ptr(f.ws), f.ws.numel()) if f is not None else (None, 0)
-        a.tiles_ws, a.tiles_ws_bytes = ptr(self.tiles_ws), self.tiles_ws.numel()
-        a.M, a.mld, a.eps = ptr(self.M), self.mld, ptr(self.eps)
-        a.out, a.flags, a.sums = ptr(per_user), ptr(flags), ptr(self.sums)
-        a.colsum_ws, a.colsum_ws_bytes = ptr(self.cs_ws), self.cs_ws.numel()
-        if user_table.dtype != torch.float32 or item_table.dtype != torch.float32 or users.dtype != torch.int32 or \
-                per_user.dtype != torch.float32 or flags.dtype != torch.int32 or row_of.dtype != torch.int32:
-            raise TypeError("nrhip_eval_pruned: float32 tables / output, int32 users / flags / row table")
-        if not (user_table.stride(1) == 1 and users.is_contiguous() and per_user.is_contiguous() and flags.is_contiguous()):
-            raise ValueError("nrhip_eval_pruned: contiguous arguments")
+        key = tuple((t.data_ptr(), t.dtype, t.shape, t.stride()) for t in (user_table, item_table, users, row_of, per_user, flags))
+        if self._last != key:
+            if self._cs_n != n:
+                nb = C.c_size_t(0)
+                call("nrhip_colsum_workspace_bytes", max(n, 1), self.nm * self.top_k, C.byref(nb))
+                if self.cs_ws is None or self.cs_ws.numel() < nb.value:
+                    self.cs_ws = torch.empty(max(nb.value, 256), dtype=torch.uint8, device=g.ws.device)
+                self._cs_n = n
+            self._item_copy = None
+            if item_table.stride(1) != 1:
+                # a temporary copy, held as long as the block points at it (a redo may reload the item side from it);
+                # nothing to remember as the key
+                item_table = self._item_copy = item_table.contiguous()
+                key = None
+            ptr = lambda t: t.data_ptr()
+            a.P, a.ldp, a.Q, a.ldq, a.d, a.cols = ptr(user_table), user_table.stride(0), ptr(item_table), item_table.stride(0), g.d, g.cols
+            a.users, a.n_users, a.batch_rows = ptr(users), n, self.batch_rows
+            a.tr_indptr, a.tr_indices = ptr(self.train.indptr), ptr(self.train.indices)
+            a.truth_indptr, a.truth_indices = ptr(self.truth.indptr), ptr(self.truth.indices)
+            a.chunk_tile, a.chunk_begin, a.n_chunks = ptr(pl.chunk_tile), ptr(pl.chunk_begin), pl.n_chunks
+            a.tile_ptr, a.plan_user, a.plan_mask, a.row_of = ptr(pl.tile_ptr), ptr(pl.user), ptr(pl.mask), ptr(row_of)
+            a.metric_ids, a.n_metric, a.top_k, a.n_keep = self.ids, self.nm, self.top_k, self.n_keep
+            a.use_filter = f.use_filter if f is not None else 0
+            a.gemm_ws, a.gemm_ws_bytes = ptr(g.ws), g.ws.numel()
+            a.filter_ws, a.filter_ws_bytes = (ptr(f.ws), f.ws.numel()) if f is not None else (None, 0)
+            a.tiles_ws, a.tiles_ws_bytes = ptr(self.tiles_ws), self.tiles_ws.numel()
+            a.M, a.mld, a.eps = ptr(self.M), self.mld, ptr(self.eps)
+            a.out, a.flags, a.sums = ptr(per_user), ptr(flags), ptr(self.sums)
+            a.colsum_ws, a.colsum_ws_bytes = ptr(self.cs_ws), self.cs_ws.numel()
+            if user_table.dtype != torch.float32 or item_table.dtype != torch.float32 or users.dtype != torch.int32 or \
+                    per_user.dtype != torch.float32 or flags.dtype != torch.int32 or row_of.dtype != torch.int32:
+                raise TypeError("nrhip_eval_pruned: float32 tables / output, int32 users / flags / row table")
+            if not (user_table.stride(1) == 1 and users.is_contiguous() and per_user.is_contiguous() and flags.is_contiguous()):
+                raise ValueError("nrhip_eval_pruned: contiguous arguments")
+        a.prepare_items = int(prepare_items)
         call("nrhip_eval_pruned", C.byref(a), _stream())
         self._last = key
         return per_user, flags, self.sums
@@ -537,17 +544,12 @@ class PrunedEvaluation:
     def redo(self, n_flagged, slab, reload_items):
         """nrhip_eval_redo behind run(): the n_flagged rows run() flagged (the count it left behind the sums, read by
         the caller) ranked again from full fp32 score rows in `slab` [rows][ld] and written over their rows of run()'s
-        per_user; the sums retaken.  reload_items: the scoring engine's item side first — 2: run() ran with
-        prepare_items = 2 on this table (only the operand copy is missing), 1: all of it.  Returns the sums tensor."""
-        from ._lib import EvalRedoArgs
+        per_user; the sums retaken.  reload_items: the scoring engine's item side first — ITEMS_OPERAND_STALE: run()
+        ran with that prepare_items on this table (only the operand copy is missing), ITEMS_STALE: all of it.  Returns
+        the sums tensor."""
         n_flagged = int(n_flagged)
         rows = min(int(slab.shape[0]), self.batch_rows)
-        dev = slab.device
-        r = getattr(self, "_redo_args", None)
-        if r is None:
-            r = self._redo_args = EvalRedoArgs()
-            self._redo_count = torch.zeros(1, dtype=torch.int32, device=dev)
-            self._redo_rows = self._redo_fixed = self._redo_ws = None
+        dev, r = slab.device, self._redo_args
         if self._redo_rows is None or self._redo_rows.shape[1] < n_flagged:
             self._redo_rows = torch.empty((2, max(n_flagged, 256)), dtype=torch.int32, device=dev)
         if self._redo_fixed is None or self._redo_fixed.shape[0] < rows:

@@ -484,7 +484,7 @@ class FullRankEvaluator:
                    by batch (scoring of batch b+1 overlapped with the ranking of batch b)."""
 
     def __init__(self, train_csr, test_csr, metric_ids, top_k, batch_rows=2048, overlap=True,
-                 pruned=True, strike_plan=True, search=None, extra_tiles=2):
+                 pruned=True, search=None, extra_tiles=2):
         # how the pruned path FINDS the tiles it rescores: "int8" (the default; tables of <= 128 columns, wider ones take
         # "bf16") = the bounded filter on the int8 matrix cores (csrc/score_i8.hip: 15-bit fixed point, exact integer
         # accumulators, the bound derived from the quantisation), "bf16" = the same on the bf16 matrix cores
@@ -495,7 +495,6 @@ class FullRankEvaluator:
         if self.search not in ("bf16", "int8", "fp32"):
             raise ValueError("search must be 'bf16', 'int8' or 'fp32', got %r" % (self.search,))
         self.extra_tiles = int(extra_tiles)  # bounded search: tiles rescored beyond top_k + 1 (room for the bound)
-        self._filter, self._filters = None, {}
         # the int8 bound is 2-4 x the bf16 form's: where scores crowd together (an untrained NGCF: a third of the rows)
         # its certificate fails row after row and every such row costs a full fp32 row.  An evaluation that had to
         # redo rows under int8 sends the next `int8_retry` evaluations through bf16 before int8 is tried again.
@@ -506,302 +505,264 @@ class FullRankEvaluator:
         # more tiles cost 0.01 ms (profiles/r05_exp_filter_i8.txt)
         self.int8_extra_tiles = 4
         self.native_loop = True              # nrhip_eval_pruned (False, tests: the same entry points issued batch by batch)
-        self._native_sums = None
         self.pruned = bool(pruned)           # tile-pruned path: no score matrix (see _evaluate_pruned)
-        self.strike_plan = bool(strike_plan)  # strikes as a planned fix-up pass after an unmasked scoring loop
-        self._plan = None                    # (False: cursors + strikes inside the scoring loop; same M bit for bit)
         self.train, self.test = train_csr, test_csr
         self.metric_ids = [int(m) for m in metric_ids]
         self.top_k = int(top_k)
         self.batch_rows = int(batch_rows)
         self.overlap = bool(overlap)         # score batch b+1 (MFMA / HBM-write bound) while batch b
-        self._gemm = None                    # is being ranked (HBM-read bound) on a second stream
-        self._scores = None
-        self._side = None
-        self._flags = None                   # pruned path: per-user "ranking may depend on ties" flags of the last run
+        self._side = None                    # is being ranked (HBM-read bound) on a second stream
+        # built for the item table's shape (all rebuilt when it changes): the scoring engine and its score slabs; the
+        # filters by arithmetic (both stay built: a paused int8 comes back) and the last one used; the native
+        # evaluations by (search, n_keep) and the last one run
+        self._gemm, self._scores = None, [None, None]
+        self._filters, self._filter, self._natives, self._native = {}, None, {}, None
+        self._items = E.ITEMS_CURRENT        # the engine's item side against this evaluation's table
+        self._plan = None                    # TileStrikePlan of the train matrix at the item count
+        # the last user list (keyed by the tensor object — held, so its address cannot be reused — and its in-place
+        # version counter): whether its users are distinct and, if so, its user -> evaluation row table
+        self._users_tag = self._users_ref = self._row_of = None
+        self._distinct = False
+        # per evaluation: the metric rows [n][M*K]; the pruned path's flags [n] and, after its Python loop, the same
+        # until the tail has redone their rows; the pinned host copy of the native [sums | flagged | uncertified]
+        self._rows_buf = self._flags_buf = self._flags = self._sums_host = None
+        self.search_used, self.n_flagged, self.n_uncertified = None, 0, 0
 
     def evaluate_factors(self, user_table, item_table, test_users, exact_mean=False, per_user=False, column_sums=False):
         """Returns float64 column means [n_metric*top_k] (or the fp32 np.mean when
         exact_mean) over `test_users` (int32 device tensor); per_user: the [n][n_metric*top_k] fp32
         matrix cpp_evaluate_matrix returns (evaluate.h:53-72), one row per test user; column_sums: the fp64 column
         SUMS, undivided (a rank's share of a sharded evaluation: the ranks' sums are added, then divided once)."""
-        want_rows = per_user
-        n = test_users.numel()
-        nm = len(self.metric_ids)
-        if self._gemm is None or self._gemm.cols != item_table.shape[0] or \
-                self._gemm.d != item_table.shape[1]:
+        n, cols = test_users.numel(), item_table.shape[0]
+        if self._gemm is None or (self._gemm.cols, self._gemm.d) != tuple(item_table.shape):
             self._gemm = E.score_gemm_for(item_table, self.batch_rows)       # (loads the item side itself)
-            # score slabs [slab_rows][I]: the materialised path's batch, the pruned path's redo rows — made when first
-            # needed, and never wider than 1 GiB (at 10^6 items a batch_rows slab would be 32 GB for rows that are
-            # almost never redone)
-            self._scores = []
-            self._filter = None
-            self._gemm_stale = False
+            self._items = E.ITEMS_CURRENT
+            self._scores, self._filters, self._filter, self._natives = [None, None], {}, None, {}
         else:
             # the scoring engine still holds the previous table's item copies: reloaded by whoever scores first — the
             # native pruned evaluation does it inside its one call (r06: a Python-level launch here, another for the
             # filter, then the native call left the device idle between them: 0.71 ms where the launches take 0.64)
-            self._gemm_stale = True
-        if want_rows or exact_mean or getattr(self, "_rows_buf", None) is None or \
-                self._rows_buf.shape != (n, nm * self.top_k) or self._rows_buf.device != test_users.device:
-            per_user = torch.empty((n, nm * self.top_k), dtype=torch.float32, device=test_users.device)
-            if not (want_rows or exact_mean):
-                self._rows_buf = per_user                 # (the sums-only form: the rows never leave this object)
+            self._items = E.ITEMS_STALE
+        width = len(self.metric_ids) * self.top_k
+        if self._rows_buf is None or self._rows_buf.shape != (n, width) or self._rows_buf.device != test_users.device:
+            self._rows_buf = torch.empty((n, width), dtype=torch.float32, device=test_users.device)
+        out = self._rows_buf
+        self._flags, self.n_flagged, self.n_uncertified = None, 0, 0
+        native = False
+        if self._pruned_applies(n, cols):
+            native = self._evaluate_pruned(user_table, item_table, test_users, out)
         else:
-            per_user = self._rows_buf
-        self._flags, self.n_flagged, self.n_uncertified, self._native_sums = None, 0, 0, None
-        self._n_rows, self._search_macs = n, float(n) * item_table.shape[0] * item_table.shape[1]
-        cols = item_table.shape[0]
-        starts = list(range(0, n, self.batch_rows))
-        if self.pruned and 2 * ((cols + 63) // 64) >= self.top_k + 2 and self.top_k <= 62 and n > 0 and \
-                not getattr(self._gemm, "wide", False):
-            self._evaluate_pruned(user_table, item_table, test_users, per_user, starts)
-        elif not self.overlap or len(starts) < 2:
-            self._reload_items(item_table)
-            for b in starts:
-                u = test_users[b:b + self.batch_rows]
-                S = self._gemm(user_table, u, out=self._slab(0, self.batch_rows))
-                E.mask_train(S, u, self.train, cols=cols)
-                E.eval_scores(S, self.test, self.metric_ids, self.top_k, users=u, cols=cols,
-                              out=per_user[b:b + u.numel()])
-        else:
-            # two score slabs, two HIP streams: GEMM + mask of batch b+1 on the current stream,
-            # top-K + metrics of batch b on the side stream; events order the slab hand-offs
-            self._reload_items(item_table)
-            self._slab(0, self.batch_rows)
-            self._slab(1, self.batch_rows)
-            if self._side is None:
-                self._side = torch.cuda.Stream(device=test_users.device)
-            main, side = torch.cuda.current_stream(), self._side
-            ranked = [None, None]                       # per slab: event "ranking finished"
-            for k, b in enumerate(starts):
-                u = test_users[b:b + self.batch_rows]
-                slab = self._scores[k % 2]
-                if ranked[k % 2] is not None:
-                    main.wait_event(ranked[k % 2])      # the slab is free again
-                S = self._gemm(user_table, u, out=slab)
-                E.mask_train(S, u, self.train, cols=cols)
-                scored = main.record_event()
-                with torch.cuda.stream(side):
-                    side.wait_event(scored)
-                    E.eval_scores(S, self.test, self.metric_ids, self.top_k, users=u, cols=cols,
-                                  out=per_user[b:b + u.numel()])
-                    ranked[k % 2] = side.record_event()
-            main.wait_stream(side)
-        if exact_mean or want_rows:
-            if self._native_sums is not None:             # the counts lie behind the sums: the redo needs no host sync of its own
-                both = self._read_native_sums()
-                self.n_flagged, self.n_uncertified = int(both[-2]), int(both[-1])
-                if self.n_flagged:
-                    self._redo_native(item_table)
-                self._flags = None
-            else:
-                self._redo_flagged(user_table, item_table, test_users, per_user)
-            self._note_flags()
-            rows = per_user.cpu().numpy()
-            return rows if want_rows else np.mean(rows, axis=0)   # uni_evaluator.py:150-151
-        div = 1 if column_sums else n
-        # ONE device->host copy per evaluation: the column sums and the number of rows flagged for ties
-        # travel together; only if some row was flagged are those rows redone and the sums retaken
-        if self._native_sums is not None:                 # nrhip_eval_pruned left the sums and the flag count together
-            both = self._read_native_sums()
-            self.n_flagged, self.n_uncertified = int(both[-2]), int(both[-1])
-            self._note_flags()
-            if self.n_flagged:
-                # the flagged rows again from full score rows and the sums retaken, in one native call (r06: the
-                # Python-level redo — index, GEMM, mask, rank, scatter, sums — cost 0.31 ms whatever the count)
-                self._redo_native(item_table)
-                both = self._read_native_sums()
-                self._flags = None
-            return both[:-2] / div
-        else:
-            sums = E.colsum(per_user)
-            if self._flags is None:
-                return sums.cpu().numpy() / div    # every mean is the fp64 column sum divided ON THE HOST (a device-side
-                #                                    scalar division may be a reciprocal multiply: last-ulp differences)
-            both = torch.cat([sums.reshape(-1), (self._flags != 0).sum().to(sums.dtype).reshape(1),
-                              ((self._flags & 2) != 0).sum().to(sums.dtype).reshape(1)]).cpu().numpy()
-        self.n_flagged, self.n_uncertified = int(both[-2]), int(both[-1])
-        self._note_flags()
-        if self.n_flagged:
-            # (both counts are known: the redo below runs without a host round trip of its own)
-            self._redo_flagged(user_table, item_table, test_users, per_user, known=(self.n_flagged, self.n_uncertified))
-            return E.colsum(per_user).cpu().numpy() / div
-        return both[:-2] / div
+            self._evaluate_materialised(user_table, item_table, test_users, out)
+        return self._finish(user_table, item_table, test_users, out, native, per_user or exact_mean,
+                            per_user, 1 if column_sums else n)
 
-    def _read_native_sums(self):
-        """[column sums | flagged rows | rows among them whose certificate failed] of the native evaluation, on the host"""
-        host = getattr(self, "_sums_host", None)
-        if host is None or host.shape != self._native_sums.shape:
-            host = self._sums_host = torch.empty(self._native_sums.shape, dtype=self._native_sums.dtype, pin_memory=True)
-        host.copy_(self._native_sums, non_blocking=True)         # (pinned: no staging copy behind the device's)
-        torch.cuda.current_stream().synchronize()
-        self._native_sums = None
-        return host.numpy().copy()
+    def _pruned_applies(self, n, cols):
+        """the tile-pruned path: top_k + 2 tiles at least (the best top_k + 1 and one to compare them with), top_k
+        within the tile selection's 62, and a scoring loop with a tile-maxima form (not the wide GEMM)"""
+        return self.pruned and n > 0 and self.top_k <= 62 and 2 * ((cols + 63) // 64) >= self.top_k + 2 and \
+            not isinstance(self._gemm, E.ScoreGemmWide)
 
-    def _redo_native(self, item_table):
-        """nrhip_eval_redo: the rows the native evaluation flagged, from full fp32 score rows (at most 1 GiB of them at a
-        time), over their rows of its output; leaves the retaken sums for _read_native_sums"""
-        step = max(1, min(self.batch_rows, (1 << 28) // max(self._gemm.ld, 1)))
-        slab = self._slab(0, min(step, self.n_flagged))
-        stale = getattr(self, "_gemm_stale", False)
-        self._native_sums = self._native.redo(self.n_flagged, slab, reload_items=2 if stale == "operand copy" else 1 if stale else 0)
-        self._gemm_stale = False
-
-    def _reload_items(self, item_table):
-        """the scoring engine's item copies, if they are still the previous table's"""
-        if getattr(self, "_gemm_stale", False):
-            self._gemm.prepare(item_table)
-            self._gemm_stale = False
-
-    def _slab(self, k, rows):
-        """score slab k with room for `rows` rows"""
-        while len(self._scores) <= k:
-            self._scores.append(None)
-        if self._scores[k] is None or self._scores[k].shape[0] < rows:
-            self._scores[k] = None
-            self._scores[k] = self._gemm.new_score_buffer(rows)
-        return self._scores[k]
-
-    def _note_flags(self):
-        # only rows whose CERTIFICATE failed (flag bit 1) say something about the int8 bound; rows flagged for ties or a
-        # full bucket would be flagged under any search (ADVICE r5: a dataset with tied rows must not lose int8 for good)
-        # ... and what a redone row costs is a fixed ~0.2 ms (a host round trip, three launches) plus one fp32 row: at the
-        # gowalla shape that is more than int8 saves over bf16 (0.1 ms), at a search of tens of milliseconds (config 4:
-        # 8,192 users x 10^6 items x 128) it is nothing — there only a run that fails every hundredth row pauses int8
-        if getattr(self, "search_used", None) == "int8" and self.search == "int8":
-            big = self._search_macs > 4e12
-            if self.n_uncertified > (self._n_rows // 100 if big else 0):
-                self._int8_pause = self.int8_retry
-
-    def _evaluate_pruned(self, user_table, item_table, test_users, per_user, starts):
-        """Level 1: tile maxima from the scoring loop (scores never stored); level 2: rescore and
-        rank the top_k+1 best tiles per user.  Rows whose ranking could depend on ties come back
-        flagged and are recomputed from full score rows — same numbers as the materialised path."""
-        n = test_users.numel()
-        # (every row's flag is WRITTEN by level 2 — remap_rank_kernel — so no fill: in steady state an evaluation
-        #  launches nothing but this package's kernels; `torch.unique` / the user -> row table below run once per user list)
-        flags = getattr(self, "_flags_buf", None)             # (read back before the next evaluation writes it)
-        if flags is None or flags.numel() != n or flags.device != test_users.device:
-            flags = self._flags_buf = torch.empty(n, dtype=torch.int32, device=test_users.device)
-        self.n_flagged = 0
-        plan = row_of = None
-        use_plan = self.strike_plan
-        if use_plan:
-            # the planned strikes look a user's row up: test_users must be distinct (uni_evaluator.py:108 hands over
-            # the keys of a dict).  Checked once per user list (one count, one host read), not per evaluation; a list
-            # with repeats takes the in-loop strikes, which have no such precondition (ADVICE r3).
-            # (keyed by the tensor object — held, so its address cannot be reused — and its in-place version counter)
-            tag = (id(test_users), test_users._version, n)
-            if getattr(self, "_distinct_tag", None) != tag:
-                self._distinct_tag, self._users_ref = tag, test_users
-                self._distinct = int(torch.unique(test_users).numel()) == n
-            use_plan = self._distinct
-        if use_plan:
-            if self._plan is None or self._plan.cols != item_table.shape[0]:
-                self._plan = E.TileStrikePlan(self.train, item_table.shape[0])
-            plan = self._plan
-            if getattr(self, "_row_of_tag", None) != tag:     # the user -> evaluation row table, once per user list
-                t = torch.full((self.train.n_rows,), -1, dtype=torch.int32, device=test_users.device)
-                t[test_users.long()] = torch.arange(n, dtype=torch.int32, device=test_users.device)
-                self._row_of_tag, self._row_of = tag, t
-            row_of = self._row_of
-        filt = None
+    def _choose_search(self, d, cols, use_plan):
+        """(search, n_keep): the arithmetic that finds the tiles to rescore this evaluation, and how many it keeps"""
         arith = self.search
-        if arith == "int8" and not E.ScoreFilter.supports(item_table.shape[1], "int8"):
+        if arith == "int8" and not E.ScoreFilter.supports(d, "int8"):
             arith = "bf16"                                    # (both forms are built for d <= 128)
         if arith == "int8" and self._int8_pause > 0:
             self._int8_pause -= 1
             arith = "bf16"                                    # the last int8 evaluation left rows uncertified
         # the int8 bound is wider: its certificate gets more rescored tiles to stand on (int8_extra_tiles more)
         extra = self.extra_tiles + (self.int8_extra_tiles if arith == "int8" else 0)
-        n_keep = min(self.top_k + 1 + extra, 63, 2 * ((item_table.shape[0] + 63) // 64) - 1)
-        if arith != "fp32" and use_plan and E.ScoreFilter.supports(item_table.shape[1], arith) and n_keep > self.top_k:
-            if self._filter is None:
-                self._filters = {}                            # (a new scoring engine: new table shape)
-            filt_stale = arith in self._filters               # both forms stay built: a paused int8 comes back
-            if not filt_stale:
-                self._filters[arith] = E.ScoreFilter(item_table, self.batch_rows, arith)     # (loads the item side itself)
-            filt = self._filter = self._filters[arith]
-        else:
-            filt_stale = False
-        self.search_used = filt.arith if filt is not None else "fp32"
-        # the item side of both engines inside the native call when both are stale (the steady state); else from here
-        native = use_plan and self.native_loop
-        inside = native and self._gemm_stale and (filt is None or filt_stale)
-        if not inside:
-            self._reload_items(item_table)
-            if filt is not None and filt_stale:
-                filt.prepare(item_table)
-        if use_plan and self.native_loop:
-            # the whole batch loop, the column sums and the flagged-row count in one native call (nrhip_eval_pruned)
-            keep = n_keep if filt is not None else self.top_k + 1
-            key = (id(self._gemm), id(filt), id(plan), keep)
-            if getattr(self, "_native_key", None) != key:
-                cache = getattr(self, "_natives", None)
-                if cache is None or cache[0] is not self._gemm:
-                    cache = self._natives = (self._gemm, {})
-                if key not in cache[1]:
-                    cache[1][key] = E.PrunedEvaluation(self._gemm, filt, plan, self.train, self.test, self.metric_ids,
-                                                       self.top_k, keep, self.batch_rows)
-                self._native, self._native_key = cache[1][key], key
-            # (with a filter the call leaves the fp32 scoring loop's operand copy alone — 2 — and the engine stays
-            #  stale: rows redone from full score rows reload it first, _reload_items)
-            _, _, self._native_sums = self._native.run(user_table, item_table, test_users, row_of, per_user, flags,
-                                                       prepare_items=(2 if filt is not None else 1) if inside else 0)
-            if not (inside and filt is not None):
-                self._gemm_stale = False
-            else:
-                self._gemm_stale = "operand copy"             # (the k-major copy is this table's)
-            self._flags = flags
-            return
-        self._native_sums = None
-        for b in starts:
-            u = test_users[b:b + self.batch_rows]
-            if filt is None:
-                M = self._gemm.tile_maxima(user_table, u, self.train, plan=plan, row_of=row_of, row_lo=b)
-                E.eval_tiles(M, user_table, self._gemm, u, self.train, self.test, self.metric_ids,
-                             self.top_k, per_user[b:b + u.numel()], flags[b:b + u.numel()])
-            else:
-                M, eps = self._gemm.tile_maxima(user_table, u, self.train, plan=plan, row_of=row_of, row_lo=b,
-                                                filt=filt)
-                E.eval_tiles(M, user_table, self._gemm, u, self.train, self.test, self.metric_ids,
-                             self.top_k, per_user[b:b + u.numel()], flags[b:b + u.numel()], eps=eps, n_keep=n_keep)
-        self._flags = flags                        # read by evaluate_factors together with the sums
+        n_keep = min(self.top_k + 1 + extra, 63, 2 * ((cols + 63) // 64) - 1)
+        # the filter leaves the train items to the planned strikes; exact maxima need only the top_k + 1 best tiles
+        if arith == "fp32" or not use_plan or not E.ScoreFilter.supports(d, arith) or n_keep <= self.top_k:
+            return "fp32", self.top_k + 1
+        return arith, n_keep
 
-    def _redo_flagged(self, user_table, item_table, test_users, per_user, known=None):
-        """Rows whose ranking could depend on ties: recomputed from full score rows.  known = (flagged rows, rows among
-        them whose certificate failed) when the caller has read the counts already (they come back with the column
-        sums): the row list is then formed on the device without a host round trip."""
-        if self._flags is None:
-            return
+    def _distinct_users(self, test_users):
+        """Whether test_users holds no user twice; if so, _row_of is its user -> evaluation row table.  The planned
+        strikes look a user's row up: test_users must be distinct (uni_evaluator.py:108 hands over the keys of a dict);
+        a list with repeats takes the in-loop strikes, which have no such precondition.  Checked once per
+        user list (one count, one host read), not per evaluation."""
+        n = test_users.numel()
+        tag = (id(test_users), test_users._version, n)
+        if self._users_tag != tag:
+            self._users_tag, self._users_ref = tag, test_users
+            self._distinct = int(torch.unique(test_users).numel()) == n
+            if self._distinct:
+                self._row_of = torch.full((self.train.n_rows,), -1, dtype=torch.int32, device=test_users.device)
+                self._row_of[test_users.long()] = torch.arange(n, dtype=torch.int32, device=test_users.device)
+        return self._distinct
+
+    def _evaluate_pruned(self, user_table, item_table, test_users, out):
+        """Level 1: tile maxima from the scoring loop (scores never stored); level 2: rescore and
+        rank the top_k+1 best tiles per user.  Rows whose ranking could depend on ties come back
+        flagged and are recomputed from full score rows — same numbers as the materialised path.
+        Returns whether the native loop ran (its flag counts and column sums are then on the device)."""
+        n, (cols, d) = test_users.numel(), item_table.shape
+        # (every row's flag is WRITTEN by level 2 — remap_rank_kernel — so no fill: in steady state an evaluation
+        #  launches nothing but this package's kernels; `torch.unique` / the user -> row table run once per user list)
+        if self._flags_buf is None or self._flags_buf.numel() != n or self._flags_buf.device != test_users.device:
+            self._flags_buf = torch.empty(n, dtype=torch.int32, device=test_users.device)
+        flags = self._flags_buf
+        plan = row_of = None
+        if self._distinct_users(test_users):
+            if self._plan is None or self._plan.cols != cols:
+                self._plan = E.TileStrikePlan(self.train, cols)
+            plan, row_of = self._plan, self._row_of
+        self.search_used, n_keep = self._choose_search(d, cols, plan is not None)
+        filt, filt_items = self._filters.get(self.search_used), E.ITEMS_STALE       # (built for an earlier table)
+        if self.search_used != "fp32":
+            if filt is None:
+                filt = self._filters[self.search_used] = E.ScoreFilter(item_table, self.batch_rows, self.search_used)
+                filt_items = E.ITEMS_CURRENT                  # (loads the item side itself)
+            self._filter = filt
+        native = plan is not None and self.native_loop
+        # the item side of both engines inside the native call when both are stale (the steady state); with a filter
+        # the call leaves the fp32 scoring loop's operand copy alone (nothing in it reads that copy): it stays stale
+        # until a redo needs it.  Otherwise it is reloaded from here.
+        prepare = E.ITEMS_CURRENT
+        if native and self._items == E.ITEMS_STALE and (filt is None or filt_items == E.ITEMS_STALE):
+            prepare = E.ITEMS_STALE if filt is None else E.ITEMS_OPERAND_STALE
+        else:
+            self._reload_items(item_table)
+            if filt is not None and filt_items == E.ITEMS_STALE:
+                filt.prepare(item_table)
+        if native:
+            # the whole batch loop, the column sums and the flagged-row count in one native call (nrhip_eval_pruned)
+            key = (self.search_used, n_keep)
+            if key not in self._natives:
+                self._natives[key] = E.PrunedEvaluation(self._gemm, filt, plan, self.train, self.test, self.metric_ids,
+                                                        self.top_k, n_keep, self.batch_rows)
+            self._native = self._natives[key]
+            self._native.run(user_table, item_table, test_users, row_of, out, flags, prepare_items=prepare)
+            self._items = E.ITEMS_OPERAND_STALE if prepare == E.ITEMS_OPERAND_STALE else E.ITEMS_CURRENT
+            return True
+        for b in range(0, n, self.batch_rows):
+            u = test_users[b:b + self.batch_rows]
+            M = self._gemm.tile_maxima(user_table, u, self.train, plan=plan, row_of=row_of, row_lo=b, filt=filt)
+            M, eps = M if filt is not None else (M, None)
+            E.eval_tiles(M, user_table, self._gemm, u, self.train, self.test, self.metric_ids, self.top_k,
+                         out[b:b + u.numel()], flags[b:b + u.numel()], eps=eps, n_keep=n_keep)
+        self._flags = flags                        # read by the tail together with the sums
+        return False
+
+    def _evaluate_materialised(self, user_table, item_table, test_users, out):
+        """Score slab -> train mask -> top-K + metrics, batch by batch.  Overlapped: two slabs, two HIP streams — GEMM
+        + mask of batch b+1 on the current stream, top-K + metrics of batch b on the side stream, events order the
+        slab hand-offs.  Otherwise (or with a single batch) the same loop on one slab and one stream, no events."""
         self._reload_items(item_table)
-        cols = item_table.shape[0]
-        redo = None
-        if known is not None and known[0] > 0:
-            try:
-                redo = torch.nonzero_static(self._flags, size=int(known[0])).flatten()
-                self.n_uncertified = int(known[1])
-            except (RuntimeError, NotImplementedError):      # (a build without the static form on this device)
-                redo = None
-        if redo is None:
-            redo = torch.nonzero(self._flags, as_tuple=False).flatten()      # host sync: only when rows were flagged
-            self.n_uncertified = int(((self._flags & 2) != 0).sum()) if redo.numel() else 0
-        self._flags = None
-        self.n_flagged = int(redo.numel())
+        n, cols, step = test_users.numel(), item_table.shape[0], self._slab_rows()
+        starts = range(0, n, step)
+        overlap = self.overlap and len(starts) > 1
+        slabs = [self._slab(k, step) for k in range(min(len(starts), 2 if overlap else 1))]
+        if overlap and self._side is None:
+            self._side = torch.cuda.Stream(device=test_users.device)
+        main = torch.cuda.current_stream()
+        side = self._side if overlap else main
+        ranked = [None, None]                           # per slab: event "ranking finished"
+        for k, b in enumerate(starts):
+            u = test_users[b:b + step]
+            if ranked[k % 2] is not None:
+                main.wait_event(ranked[k % 2])          # the slab is free again
+            S = self._gemm(user_table, u, out=slabs[k % len(slabs)])
+            E.mask_train(S, u, self.train, cols=cols)
+            with torch.cuda.stream(side):
+                if overlap:
+                    side.wait_event(main.record_event())        # the slab is scored
+                E.eval_scores(S, self.test, self.metric_ids, self.top_k, users=u, cols=cols, out=out[b:b + u.numel()])
+                if overlap:
+                    ranked[k % 2] = side.record_event()
+        if overlap:
+            main.wait_stream(side)
+
+    def _finish(self, user_table, item_table, test_users, out, native, want_rows, per_user, div):
+        """ONE device->host copy of [column sums | flagged rows | uncertified rows] per evaluation; only if some row was
+        flagged are those rows redone and the sums read again.  Returns the rows, their fp32 mean or the fp64 sums /
+        div — every mean divided ON THE HOST (a device-side scalar division may be a reciprocal multiply: last-ulp
+        differences)."""
+        both = self._read_sums(out, native, not want_rows)
+        self.n_flagged, self.n_uncertified = int(both[-2]), int(both[-1])
+        # only rows whose CERTIFICATE failed (flag bit 1) say something about the int8 bound; rows flagged for ties or a
+        # full bucket would be flagged under any search (ADVICE r5: a dataset with tied rows must not lose int8 for good)
+        # ... and what a redone row costs is a fixed ~0.2 ms (a host round trip, three launches) plus one fp32 row: at the
+        # gowalla shape that is more than int8 saves over bf16 (0.1 ms), at a search of tens of milliseconds (config 4:
+        # 8,192 users x 10^6 items x 128) it is nothing — there only a run that fails every hundredth row pauses int8
+        n = test_users.numel()
+        big = n * item_table.shape[0] * item_table.shape[1] > 4e12
+        if self.search_used == "int8" and self.search == "int8" and self.n_uncertified > (n // 100 if big else 0):
+            self._int8_pause = self.int8_retry
         if self.n_flagged:
-            fixed = torch.empty((self.n_flagged, per_user.shape[1]), dtype=torch.float32,
-                                device=per_user.device)
-            # full fp32 rows, at most 1 GiB of them at a time
-            step = max(1, min(self.batch_rows, (1 << 28) // max(self._gemm.ld, 1)))
-            for lo in range(0, self.n_flagged, step):
-                idx = redo[lo:lo + step]
-                u = test_users[idx].contiguous()
-                S = self._gemm(user_table, u, out=self._slab(0, min(step, self.n_flagged)))
-                E.mask_train(S, u, self.train, cols=cols)
-                E.eval_scores(S, self.test, self.metric_ids, self.top_k, users=u, cols=cols,
-                              out=fixed[lo:lo + u.numel()])
-            per_user[redo] = fixed                                       # plumbing copy of the rows
+            # (both counts are known: the redo runs without a host round trip of its own)
+            if native:                                  # nrhip_eval_redo: the sums are retaken behind the rows
+                self._native.redo(self.n_flagged, self._slab(0, min(self._slab_rows(), self.n_flagged)), self._items)
+                self._items = E.ITEMS_CURRENT
+            else:
+                self._redo_flagged(user_table, item_table, test_users, out)
+            if not want_rows:
+                both = self._read_sums(out, native, True)
+        if want_rows:
+            rows = out.cpu().numpy()
+            return rows if per_user else np.mean(rows, axis=0)   # uni_evaluator.py:150-151
+        return both[:-2] / div
+
+    def _read_sums(self, out, native, want_sums):
+        """[column sums | flagged rows | rows among them whose certificate failed] on the host, in one copy: the native
+        evaluation's (nrhip_eval_pruned / nrhip_eval_redo leave them together), else the column sums if wanted and the
+        counts of the pruned path's flags (zero without flags)"""
+        if native:
+            return self._read_native_sums()
+        sums = [E.colsum(out)] if want_sums else []
+        if self._flags is None:
+            return np.append(sums[0].cpu().numpy() if sums else [], [0.0, 0.0])
+        f = self._flags
+        counts = [(f != 0).sum().to(torch.float64).reshape(1), ((f & 2) != 0).sum().to(torch.float64).reshape(1)]
+        return torch.cat(sums + counts).cpu().numpy()
+
+    def _read_native_sums(self):
+        """_read_sums of the native evaluation"""
+        sums = self._native.sums
+        if self._sums_host is None or self._sums_host.shape != sums.shape:
+            self._sums_host = torch.empty(sums.shape, dtype=sums.dtype, pin_memory=True)
+        self._sums_host.copy_(sums, non_blocking=True)           # (pinned: no staging copy behind the device's)
+        torch.cuda.current_stream().synchronize()
+        return self._sums_host.numpy().copy()
+
+    def _redo_flagged(self, user_table, item_table, test_users, out):
+        """The rows the Python loop flagged (n_flagged of them, counted by the tail): recomputed from full score rows.
+        The row list is formed on the device without a host round trip."""
+        self._reload_items(item_table)
+        try:
+            redo = torch.nonzero_static(self._flags, size=self.n_flagged).flatten()
+        except (RuntimeError, NotImplementedError):      # (a build without the static form on this device)
+            redo = torch.nonzero(self._flags, as_tuple=False).flatten()
+        self._flags = None
+        cols, step = item_table.shape[0], self._slab_rows()
+        fixed = torch.empty((self.n_flagged, out.shape[1]), dtype=torch.float32, device=out.device)
+        slab = self._slab(0, min(step, self.n_flagged))
+        for lo in range(0, self.n_flagged, step):
+            u = test_users[redo[lo:lo + step]].contiguous()
+            S = self._gemm(user_table, u, out=slab)
+            E.mask_train(S, u, self.train, cols=cols)
+            E.eval_scores(S, self.test, self.metric_ids, self.top_k, users=u, cols=cols, out=fixed[lo:lo + u.numel()])
+        out[redo] = fixed                                       # plumbing copy of the rows
+
+    def _reload_items(self, item_table):
+        """the scoring engine's item copies, if they are still the previous table's"""
+        if self._items != E.ITEMS_CURRENT:
+            self._gemm.prepare(item_table)
+            self._items = E.ITEMS_CURRENT
+
+    def _slab_rows(self):
+        """rows per score slab: batch_rows, but never more than 1 GiB of scores (at 10^6 items a batch_rows slab would
+        be 32 GB, for rows that are almost never redone); rows are independent, so the results do not depend on it"""
+        return max(1, min(self.batch_rows, (1 << 28) // self._gemm.ld))
+
+    def _slab(self, k, rows):
+        """score slab k (of two) with room for `rows` rows"""
+        if self._scores[k] is None or self._scores[k].shape[0] < rows:
+            self._scores[k] = None
+            self._scores[k] = self._gemm.new_score_buffer(rows)
+        return self._scores[k]
 
 
 class NGCFEngine:

@@ -542,11 +542,13 @@ def test_ties_that_cannot_change_a_metric_do_not_send_a_row_to_the_replay():
     a = full.evaluate_factors(Pd, Qd, ud, exact_mean=True)
     for search in ("bf16", "fp32"):
         lean = FullRankEvaluator(trc, tec, [1, 2, 3, 4, 5], 20, batch_rows=256, search=search)
-        b = lean.evaluate_factors(Pd, Qd, ud, exact_mean=True)
-        np.testing.assert_array_equal(a, b)
-        # nearly every user has a tied pair among its 20 best (half of the top items are duplicated); few of those
-        # pairs involve a test item or the cut
-        assert 0 < lean.n_flagged < len(users) // 3, lean.n_flagged
+        # the same items once more as a transposed view: the native call loads them from a contiguous copy of its own
+        for items in (Qd, Qd.t().contiguous().t()):
+            b = lean.evaluate_factors(Pd, items, ud, exact_mean=True)
+            np.testing.assert_array_equal(a, b)
+            # nearly every user has a tied pair among its 20 best (half of the top items are duplicated); few of those
+            # pairs involve a test item or the cut
+            assert 0 < lean.n_flagged < len(users) // 3, lean.n_flagged
 
 
 @pytest.mark.parametrize("search", ["bf16", "fp32"])
@@ -578,6 +580,58 @@ def test_the_native_batch_loop_equals_the_python_batch_loop(search):
         np.testing.assert_array_equal(a.evaluate_factors(Pd, Qd, ud, exact_mean=True),
                                       b.evaluate_factors(Pd, Qd, ud, exact_mean=True))
     assert a._native is not None and getattr(b, "_native", None) is None
+
+
+@pytest.mark.parametrize("search", ["int8", "bf16", "fp32"])
+def test_an_evaluation_in_steady_state_is_one_native_call(monkeypatch, search):
+    """The entry points an evaluation issues (every one goes through engine.call): once the evaluator is built, an
+    evaluation of fresh tables of the same shape is nrhip_eval_pruned alone, whatever result it returns; rows flagged
+    for ties add one nrhip_eval_redo; a user list with repeats takes the Python batch loop, not nrhip_eval_pruned."""
+    import torch
+    import scipy.sparse as sp
+    from neurec_amd import engine as E
+    from neurec_amd.trainer import FullRankEvaluator
+    names, real = [], E.call
+
+    def record(name, *args):
+        names.append(name)
+        return real(name, *args)
+    monkeypatch.setattr(E, "call", record)
+
+    def issued(ev, P, Q, users, **kw):
+        del names[:]
+        ev.evaluate_factors(P, Q, users, **kw)
+        return list(names)
+    rng = np.random.RandomState(13)
+    U, I, d = 500, 4000, 32
+    tr = sp.random(U, I, 0.005, random_state=1, format="csr", dtype=np.float32); tr.data[:] = 1.0
+    te = sp.random(U, I, 0.004, random_state=2, format="csr", dtype=np.float32)
+    te = te - te.multiply(tr); te.eliminate_zeros(); te.sort_indices()
+    users = np.flatnonzero(np.diff(te.indptr) > 0).astype(np.int32)
+    trc, tec = E.DeviceCSR.from_scipy(tr), E.DeviceCSR.from_scipy(te)
+    ud = torch.from_numpy(users).cuda()
+
+    def tables(tied=False):
+        P = (rng.randn(U, d) * 0.1).astype(np.float32)
+        Q = (rng.randn(I, d) * 0.1).astype(np.float32)
+        if tied:
+            Q[1000:2000] = Q[:1000]                     # exact duplicates: rows flagged for their ties
+        return torch.from_numpy(P).cuda(), torch.from_numpy(Q).cuda()
+    ev = FullRankEvaluator(trc, tec, [1, 2, 3, 4, 5], 20, batch_rows=128, search=search)
+    ev.int8_retry = 0                                   # (no int8 pause: every evaluation searches the same way)
+    issued(ev, *tables(), ud)                           # builds the engine, the plan, the filter, the native call
+    for kw in ({}, {"column_sums": True}, {"exact_mean": True}, {"per_user": True}):
+        assert issued(ev, *tables(), ud, **kw) == ["nrhip_eval_pruned"], kw
+        assert ev.n_flagged == 0
+    P, Q = tables(tied=True)
+    issued(ev, P, Q, ud)                                # (the first redo sizes its workspace)
+    for kw in ({}, {"per_user": True}):
+        assert issued(ev, P.clone(), Q.clone(), ud, **kw) == ["nrhip_eval_pruned", "nrhip_eval_redo"], kw
+        assert ev.n_flagged > 0
+    repeats = torch.from_numpy(np.concatenate([users, users[:5]])).cuda()
+    for kw in ({}, {"exact_mean": True}):
+        assert "nrhip_eval_pruned" not in issued(ev, P.clone(), Q.clone(), repeats, **kw)
+        assert ev.search_used == "fp32"
 
 
 def test_nan_user_rows_do_not_disturb_the_other_users():
