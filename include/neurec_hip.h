@@ -1052,6 +1052,32 @@ int nrhip_colsum_rows(const float* d_X, int64_t ld, int rows, int cols, float* d
 int nrhip_vae_dwq0_wide(const int64_t* d_indptr, const int32_t* d_indices, const int32_t* d_rows, int batch,
                         int width, const float* d_h0val, const float* d_DA1, float* d_dWq0, void* stream);
 
+/* ---- WRMF (implicit ALS) ---------------------------------------------------
+ * Replaces: the per-row update_user / update_item solves of WRMF.py:47-59 (one tf.linalg.solve + scatter_update per
+ * row, driven by train_model, WRMF.py:66-84).  A half-sweep solves, for every row u of one side, against the other
+ * side's table Y [n_other][d]:
+ *     (Y^T Y + alpha sum_{j in N(u)} y_j y_j^T + lambda I) x_u = (1 + alpha) sum_{j in N(u)} y_j
+ * N(u) = the row's columns in the train CSR (only the pattern counts: Pui = 1, Cui = alpha).  A row without columns
+ * gets x = 0.  d = 1..128 (above: NRHIP_ERR_UNSUPPORTED); lambda > 0 and alpha >= 0 (else NRHIP_ERR_ARG).  Every sum
+ * is taken in a fixed order: results are bit-identical from run to run. */
+#define NRHIP_WRMF_CHUNK 1024 /* neighbour lists longer than this are accumulated in chunks of this many */
+/* Host-side chunk plan of a CSR (h_indptr: n_rows + 1 entries, host memory): h_row_chunk[r] = index of row r's first
+ * chunk, or -1 for rows of at most NRHIP_WRMF_CHUNK columns; h_chunk_row[c] = the row of chunk c (a row's chunks are
+ * consecutive, in list order).  Either array may be NULL (call once with both NULL to learn *n_chunks). */
+int nrhip_wrmf_chunk_plan(const int64_t* h_indptr, int n_rows, int32_t* h_row_chunk, int32_t* h_chunk_row,
+                          int* n_chunks);
+/* Scratch for nrhip_wrmf_gram and for nrhip_wrmf_solve with n_chunks chunks (one buffer serves both). */
+int nrhip_wrmf_workspace_bytes(int d, int n_chunks, size_t* bytes);
+/* d_G [d][d] = d_Y^T d_Y over the n rows of d_Y [n][d] (YTY / XTX, WRMF.py:47 / 54). */
+int nrhip_wrmf_gram(const float* d_Y, int n, int d, float* d_G, void* d_ws, size_t ws_bytes, void* stream);
+/* The half-sweep: d_X [n_rows][d] row u = the solve above, rows u of the CSR (d_indptr int64, d_indices int32 column
+ * ids < n_other), d_G from nrhip_wrmf_gram of the same d_Y; d_row_chunk / d_chunk_row: the chunk plan of this CSR
+ * (device copies; may be NULL when n_chunks = 0).  d_X must not alias d_Y. */
+int nrhip_wrmf_solve(const int64_t* d_indptr, const int32_t* d_indices, int n_rows, const float* d_Y, int n_other,
+                     const float* d_G, int d, float alpha, float lambda, const int32_t* d_row_chunk,
+                     const int32_t* d_chunk_row, int n_chunks, float* d_X, void* d_ws, size_t ws_bytes,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

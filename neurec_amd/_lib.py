@@ -299,6 +299,10 @@ SIGNATURES = {
     "nrhip_div_scalar": [p, f32, p, i64, p],
     "nrhip_add2d": [p, i64, p, i64, p, i64, i64, i32, p],
     "nrhip_copy2d": [p, i64, p, i64, i64, i32, p],
+    "nrhip_wrmf_chunk_plan": [p, i32, p, p, C.POINTER(i32)],
+    "nrhip_wrmf_workspace_bytes": [i32, i32, psz],
+    "nrhip_wrmf_gram": [p, i32, i32, p, p, sz, p],
+    "nrhip_wrmf_solve": [p, p, i32, p, i32, p, i32, f32, f32, p, p, i32, p, p, sz, p],
 }
 
 for _name, _args in SIGNATURES.items():
