@@ -1,4 +1,4 @@
-// spmm_blocked.hip — persistent-workgroup, lane-group SpMM  Y = Â·X  for d = 64 / 128 / 256
+// spmm_blocked.hip — persistent-workgroup, lane-group SpMM  Y = Â·X  for d = 16 / 32 / 64 / 128 / 256
 // (optionally cache-blocked by column windows).
 //
 // Why: at the gowalla shape one pass gathers 1.62 M rows of 256 B (415 MB) out of an 18 MB
@@ -9,10 +9,11 @@
 // instruction moves four rows (16 lanes × 16 B each) instead of one
 // (scripts/exp_gather_blocked.py).  This kernel is built on those two facts.
 //
-// Schedule (host, once per matrix):
+// Schedule (host, once per matrix; built by spmm_blocked_plan.h, which holds the reasons stage by stage):
 //   * one workgroup per CU (16 waves), workgroup b on XCD b % 8.  With a bipartite split the
 //     user rows go to XCDs 0-3 and the item rows to XCDs 4-7 (they gather from disjoint halves
-//     of the table); each workgroup owns a contiguous run of rows, balanced by non-zeros;
+//     of the table); the rows of a class are dealt to its workgroups by cost, longest first, so a
+//     workgroup owns a LIST of rows (row_of) and every workgroup carries the same cost;
 //   * the column range a class gathers from is cut into K blocks of ≤ block_bytes; a row's
 //     non-zeros (ascending columns) fall into ≤ K contiguous sub-lists, one per block;
 //   * phase k of the kernel walks the sub-lists of block k.  All workgroups of an XCD move
@@ -26,84 +27,36 @@
 // after the phase (deterministic; only such hub rows deviate from the sequential order).
 // Epilogue as in spmm.hip: y += addend, sum_out = sum_in + y.
 #include "nr_common.h"
+#include "spmm_blocked_plan.h"
 #include <algorithm>
 #include <new>
 #include <cstdlib>
-#include <queue>
-#include <functional>
-#include <utility>
+#include <initializer_list>
 #include <vector>
 
 namespace {
 
-constexpr int kSegDefault = 64;     // longest sub-list one lane group walks alone
-constexpr int kRMaxDefault = 416;   // row accumulators per workgroup (104 KB)
-constexpr int kPMaxDefault = 192;   // segment partial slots per workgroup and phase (48 KB)
-constexpr int kMaxPhases = 32;
-constexpr int kMaxLdsBytes = 160 * 1024;
+using nr_plan::kMaxLdsBytes;
+using nr_plan::blocked_plan_bytes;
+static_assert((int)nr_plan::kOk == NR_OK && (int)nr_plan::kErrArg == NR_ERR_ARG &&
+              (int)nr_plan::kErrUnsupported == NR_ERR_UNSUPPORTED, "the planner returns the C ABI's status codes");
 
-struct BlockedPlan {
+// The plan behind the C handle: the device addresses of the schedule's arrays (spmm_blocked_plan.h, where the
+// layout of the buffer is listed) and the scalars the launches need.
+struct BlockedPlan : nr_plan::PlanArrays<int4> {
   int64_t n_rows, nnz, n_ent, n_cmb;
   int n_wg, n_phases;
   int seg, r_max, p_max, waves, d;
-  int32_t* wg_row0;      // first position of the workgroup's rows in row_of
-  int32_t* wg_nrows;
-  // r05: the rows of a workgroup are a LIST, not a run: row_of[wg_row0[w] + slot] (see "dealt rows" at the plan
-  // builder) — and the plan owns the (column, value) pairs in that order, so a workgroup's pairs stay one
-  // contiguous slice (the staged masked kernel reads it in bulk).  ent[].z / wg_nnz index the packed arrays.
-  int32_t* row_of;       // [n_rows]
-  uint32_t* pk_src;      // [n_rows] first CSR position of row_of[k]
-  uint32_t* pk_dst;      // [n_rows + 1] first packed position of row_of[k]
-  int32_t* pk_idx;       // [nnz]
-  float* pk_val;         // [nnz]
   const int32_t* pk_from_idx;   // the CSR arrays the packed copy was made from (nullptr: not yet)
   const float* pk_from_val;
-  int32_t* wg_ent_off;   // [n_wg][n_phases + 1]
-  int32_t* wg_cmb_off;   // [n_wg][n_phases + 1]
-  int4* ent;             // {accumulator slot, length, first non-zero (packed), owning row (global id)}
-  int4* cmb;             // {row slot, first partial slot, segments, row (global id)}
   // masked hops of a training step (d = 64, one phase): dedicated kernels below
-  uint32_t* wg_nnz;      // [n_wg][2] first non-zero of the workgroup's rows, count
   int nnz_cap, ent_cap;  // largest slice / descriptor list of a workgroup
   int colmask_ok;
-  // wanted-rows schedule (row-masked hop): the same sub-lists dealt to the workgroups by descending
-  // row length, descriptors carry global rows
-  int4* w_ent;           // {0 | r_max + partial slot, length, first non-zero, row}
-  int4* w_cmb;           // {row, first partial slot, segments, 0}
-  int32_t* w_ent_off;    // [n_wg][2]
-  int32_t* w_cmb_off;    // [n_wg][2]
-  int wanted_ok, w_ent_cap, w_nnz_cap, w_bitmap_words;
-  // wave-cooperative row-masked hop (spmm_wanted_wave_kernel): units dealt by descending length; a row
-  // of > 64 non-zeros is cut into 64-segments grouped in chunks of <= 8 consecutive segments, each
-  // chunk a unit of its own (a hub's bytes spread over several CUs); partial sums in global memory
-  int ww_ok, ww_ent_cap;
-  int32_t* ww_off;       // [n_wg + 1] entries
-  int32_t* ww_choff;     // [n_wg + 1] chunks
-  int4* ww_ent;          // {0 | 1 + global partial slot | -(1 + LDS slot), length, first non-zero, row}
-  int32_t* ww_gch;       // hub index of every chunk
-  int4* ww_hub;          // {row, first partial slot, segments, chunks}
-  int32_t* ww_lcoff;     // [n_wg + 1] one-chunk rows (segment sums stay in LDS)
-  int4* ww_lcmb;         // {row, first LDS slot, segments, 0}
+  int wanted_ok, w_ent_cap, w_nnz_cap, w_bitmap_words;      // staged wanted-rows schedule (row-masked hop)
+  int ww_ok, ww_ent_cap;                                    // wave-cooperative row-masked hop
   int ww_lds_slots;      // LDS partial slots per workgroup
-  float* ww_part;        // [segments of multi-chunk rows][64]
-  unsigned* ww_cnt;      // [multi-chunk rows] chunks finished (zero between launches)
 };
 
-size_t blocked_plan_bytes(int64_t n_rows, int64_t nnz) {
-  const size_t max_ent = (size_t)std::min<int64_t>(nnz, n_rows * (int64_t)kMaxPhases) + (size_t)(nnz / 16) + 64;
-  const size_t max_cmb = (size_t)(nnz / 16) + 64;
-  const size_t wg = 4096 + (size_t)(n_rows / 32);   // generous bound on workgroups
-  const size_t w_ent = (size_t)n_rows + (size_t)(nnz / 16) + 64;        // wanted-rows schedule (one phase)
-  // wave-cooperative wanted-rows schedule: an entry per row or 64-segment, a partial row per segment
-  const size_t ww_seg = (size_t)(nnz / 32) + 64, ww_ents = (size_t)n_rows + ww_seg;
-  const size_t ww = 3 * nr_align_up((wg + 1) * 4, 256) + nr_align_up(ww_ents * 16 + 16, 256) +
-                    nr_align_up(ww_seg * 4 + 4, 256) + 2 * nr_align_up(max_cmb * 16 + 16, 256) +
-                    nr_align_up(ww_seg * 256 + 256, 256) + nr_align_up(max_cmb * 4 + 4, 256);
-  const size_t dealt = 3 * nr_align_up(((size_t)n_rows + 1) * 4, 256) + 2 * nr_align_up((size_t)nnz * 4 + 4, 256);
-  return ww + dealt + nr_align_up(max_ent * 16, 256) + nr_align_up(max_cmb * 16, 256) +
-         3 * nr_align_up(wg * 8, 256) + 2 * nr_align_up(wg * (kMaxPhases + 1) * 4, 256) +
-         nr_align_up(w_ent * 16, 256) + nr_align_up(max_cmb * 16, 256) + 2 * nr_align_up(wg * 8, 256);
-}
 
 // Optional fused optimiser epilogue (last backward hop of a LightGCN step): instead of storing
 // y, treat g = y + grad_b[row] as the dense gradient of `var` and apply TF-1.12 ApplyAdam to the
@@ -1025,7 +978,6 @@ int launch_wanted_wave(const BlockedPlan* p, const int32_t* d_indices, const flo
   return NR_OK;
 }
 
-struct HostEnt { int32_t slot, len; uint32_t begin; int32_t owner; };
 int s_gathers_in_flight = 8;     // tuning knob (nrhip_spmm_blocked_tune)
 
 // (column, value) pairs copied into the plan's row order: row k of the order is CSR positions
@@ -1044,6 +996,35 @@ __global__ __launch_bounds__(256) void row_order_pack_kernel(const uint32_t* __r
   }
 }
 
+// The kernels of this plan's width may use the LDS their schedule needs (more than the 64 KB a kernel gets unasked).
+static hipError_t allow_plan_lds(const BlockedPlan* p) {
+  hipError_t e = hipSuccess;
+  auto allow = [&](const void* fn, size_t lds) {
+    if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  };
+  const size_t lds = (size_t)(p->r_max + p->p_max) * p->d * 4 + (size_t)p->r_max * 4;   // accumulators + the workgroup's row list
+#define NR_ALLOW(DD)                                                                                                         \
+  allow((const void*)spmm_blocked_kernel<false, 16, 8, DD>, lds); allow((const void*)spmm_blocked_kernel<true, 16, 8, DD>, lds); \
+  allow((const void*)spmm_blocked_kernel<false, 16, 4, DD>, lds); allow((const void*)spmm_blocked_kernel<true, 16, 4, DD>, lds); \
+  allow((const void*)spmm_blocked_kernel<false, 8, 8, DD>, lds); allow((const void*)spmm_blocked_kernel<true, 8, 8, DD>, lds);   \
+  allow((const void*)spmm_blocked_kernel<false, 8, 4, DD>, lds); allow((const void*)spmm_blocked_kernel<true, 8, 4, DD>, lds)
+  if (p->d == 16) { NR_ALLOW(16); } else if (p->d == 32) { NR_ALLOW(32); }
+  else if (p->d == 64) {
+    NR_ALLOW(64);
+    allow((const void*)spmm_blocked_kernel<false, 16, 8, 64, true>, lds);
+  }
+  else if (p->d == 128) { NR_ALLOW(128); } else { NR_ALLOW(256); }
+#undef NR_ALLOW
+  if (p->wanted_ok) allow((const void*)spmm_wanted_rows_kernel, wanted_lds_bytes(p));
+  if (p->ww_ok) allow((const void*)spmm_wanted_wave_kernel, ww_lds_bytes(p));
+  if (p->colmask_ok)
+    for (const void* fn : {(const void*)spmm_staged_masked_kernel<true, false>,
+                           (const void*)spmm_staged_masked_kernel<false, true>,
+                           (const void*)spmm_staged_masked_kernel<true, true>})
+      allow(fn, colmask_lds_bytes(p));
+  return e;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1060,16 +1041,10 @@ int nrhip_spmm_blocked_plan_create(const int64_t* h_indptr, const int32_t* h_ind
                                    int n_workgroups, int waves_per_wg, int seg_len, int r_max,
                                    int p_max, void* d_plan_buf, size_t plan_bytes, void* stream,
                                    void** plan_out) {
-  const int kWaves = waves_per_wg > 0 ? waves_per_wg : 16;
-  const int kSeg = seg_len > 0 ? seg_len : kSegDefault;
-  const int kD = d;
-  const int kRMax = r_max > 0 ? r_max : kRMaxDefault * kWaves / 16 * 64 / (d > 0 ? d : 64);
-  const int kPMax = p_max > 0 ? p_max : kPMaxDefault * kWaves / 16 * 64 / (d > 0 ? d : 64);
-  NR_REQUIRE(d == 16 || d == 32 || d == 64 || d == 128 || d == 256, NR_ERR_UNSUPPORTED,
-             "spmm_blocked: embedding dim %d not built (16, 32, 64, 128, 256)", d);
-  NR_REQUIRE(kWaves == 16 || kWaves == 8, NR_ERR_UNSUPPORTED, "spmm_blocked: waves per workgroup %d (8, 16)", kWaves);
-  NR_REQUIRE(kSeg >= 16 && (size_t)(kRMax + kPMax) * kD * 4 + (size_t)kRMax * 4 <= (size_t)kMaxLdsBytes, NR_ERR_UNSUPPORTED,
-             "spmm_blocked: seg %d / accumulators %d+%d do not fit", kSeg, kRMax, kPMax);
+  nr_plan::Options opt;
+  nr_plan::Error err;
+  int rc = nr_plan::resolve_options(d, waves_per_wg, seg_len, r_max, p_max, block_bytes, split_row, n_rows, &opt, &err);
+  NR_REQUIRE(rc == NR_OK, rc, "%s", err.msg.c_str());
   NR_REQUIRE(h_indptr && h_indices && d_plan_buf && plan_out && n_rows > 0, NR_ERR_ARG,
              "spmm_blocked_plan_create: bad arguments");
   const int64_t nnz = h_indptr[n_rows] - h_indptr[0];
@@ -1078,458 +1053,52 @@ int nrhip_spmm_blocked_plan_create(const int64_t* h_indptr, const int32_t* h_ind
   const size_t need_bytes = blocked_plan_bytes(n_rows, nnz);
   NR_REQUIRE(plan_bytes >= need_bytes, NR_ERR_WORKSPACE,
              "spmm_blocked_plan_create: plan buffer %zu < %zu bytes", plan_bytes, need_bytes);
-  if (block_bytes <= 0) block_bytes = (int64_t)1 << 40;     // measured: phases cost more than they save
-  if (split_row <= 0 || split_row >= n_rows) split_row = 0;
   int n_wg = n_workgroups;
-  if (n_wg <= 0) {
+  if (n_wg <= 0) {                                           // one workgroup per CU
     int dev = 0;
     hipDeviceProp_t prop;
     NR_CHECK_HIP(hipGetDevice(&dev));
     NR_CHECK_HIP(hipGetDeviceProperties(&prop, dev));
-    n_wg = prop.multiProcessorCount * (16 / kWaves);
+    n_wg = prop.multiProcessorCount * (16 / opt.waves);
   }
-  n_wg = n_wg / 8 * 8;
-  if (n_workgroups <= 0 && n_wg >= 8) {
-    // more rows than one workgroup per CU can hold accumulators for: launch a multiple of the CU
-    // count (the extra workgroups queue behind the resident ones; without column blocking the
-    // rounds are independent)
-    const int64_t per_class = split_row ? n_wg / 2 : n_wg;
-    const int64_t biggest = split_row ? std::max<int64_t>(split_row, n_rows - split_row) : n_rows;
-    const int64_t cap = (int64_t)kRMax * 9 / 10;
-    const int64_t mult = (biggest + per_class * cap - 1) / (per_class * cap);
-    if (mult > 1) n_wg = (int)std::min<int64_t>((int64_t)n_wg * mult, 4096 + n_rows / 32) / 8 * 8;
-  }
-  NR_REQUIRE(n_wg >= 8 && n_wg <= 4096 + n_rows / 32, NR_ERR_UNSUPPORTED, "spmm_blocked: %d workgroups",
-             n_wg);
+  rc = nr_plan::choose_workgroup_count(n_wg, n_workgroups <= 0, n_rows, &opt, &err);
+  NR_REQUIRE(rc == NR_OK, rc, "%s", err.msg.c_str());
+  // "0" switches a kernel family off for A/B runs against the general kernel / the staged lane-group walker
+  const char* env = getenv("NEUREC_SPMM_MASKED_FAST");
+  opt.masked_fast = !(env && env[0] == '0');
+  env = getenv("NEUREC_SPMM_WANTED_WAVE");
+  opt.wanted_wave = !(env && env[0] == '0');
+  env = getenv("NEUREC_SPMM_WANTED_NNZ_CAP");                // tests: force the chunked path
+  opt.wanted_nnz_cap = env ? std::max(atoi(env), 1) : 0;
 
-  // cost of a row for balancing: its non-zeros plus a fixed cost per sub-list (descriptor, first
-  // index chunk and the short last gather round; fitted on the per-workgroup timeline,
-  // profiles/r01_exp_spmm_timeline.txt)
-  const int ent_cost = 4;     // r05 (rows dealt): 0 .. 16 all within 1 us of each other, 2-4 best (profiles/r05_exp_entcost.txt)
-  auto row_cost = [&](int64_t l) { return l + (int64_t)ent_cost * std::max<int64_t>(1, (l + kSeg - 1) / kSeg); };
-  struct ClassDesc { int64_t ra, rb; std::vector<int> wgs; int32_t cmin; int64_t width, K; };
-  std::vector<ClassDesc> classes;
-  if (split_row) {
-    ClassDesc a{0, split_row, {}, 0, 1, 1}, b{split_row, n_rows, {}, 0, 1, 1};
-    // workgroups per class in proportion to the class's cost; class A fills XCDs 0.. first
-    // (workgroup w runs on XCD w % 8), so at most one XCD serves both halves of the table
-    int64_t cost_a = 0, cost_b = 0;
-    for (int64_t r = 0; r < n_rows; ++r) (r < split_row ? cost_a : cost_b) += row_cost(h_indptr[r + 1] - h_indptr[r]);
-    int n_a = (int)((double)n_wg * (double)cost_a / (double)std::max<int64_t>(cost_a + cost_b, 1) + 0.5);
-    n_a = std::min(std::max(n_a, 1), n_wg - 1);
-    {
-      // every class must still fit its rows into its workgroups' accumulators
-      const int64_t cap = (int64_t)kRMax * 9 / 10;
-      const int need_a = (int)((split_row + cap - 1) / cap), need_b = (int)((n_rows - split_row + cap - 1) / cap);
-      n_a = std::max(n_a, std::min(need_a, n_wg - 1));
-      n_a = std::min(n_a, std::max(n_wg - need_b, 1));
-    }
-    std::vector<int> order;                    // workgroup ids, XCD-major
-    for (int x = 0; x < 8; ++x)
-      for (int w = x; w < n_wg; w += 8) order.push_back(w);
-    for (int i = 0; i < n_wg; ++i) (i < n_a ? a : b).wgs.push_back(order[i]);
-    std::sort(a.wgs.begin(), a.wgs.end());
-    std::sort(b.wgs.begin(), b.wgs.end());
-    classes.push_back(a);
-    classes.push_back(b);
-  } else {
-    ClassDesc a{0, n_rows, {}, 0, 1, 1};
-    for (int w = 0; w < n_wg; ++w) a.wgs.push_back(w);
-    classes.push_back(a);
-  }
-  std::vector<int32_t> wg_row0(n_wg, 0), wg_nrows(n_wg, 0);
-  std::vector<std::vector<std::vector<HostEnt>>> wg_ent(n_wg);     // [wg][phase][entries]
-  std::vector<std::vector<std::vector<int4>>> wg_cmb(n_wg);
-  int n_phases = 1;
-  std::vector<std::vector<int32_t>> wg_rows((size_t)n_wg);         // [wg] its rows, slot order
-  for (ClassDesc& cl : classes) {
-    const int64_t cb = h_indptr[cl.ra], ce = h_indptr[cl.rb];
-    int32_t cmin = INT32_MAX, cmax = -1;
-    for (int64_t t = cb; t < ce; ++t) {
-      cmin = std::min(cmin, h_indices[t]);
-      cmax = std::max(cmax, h_indices[t]);
-    }
-    if (cmax < cmin) { cmin = 0; cmax = 0; }
-    const int64_t span = (int64_t)cmax + 1 - cmin;
-    int64_t K = (span * kD * 4 + block_bytes - 1) / block_bytes;
-    K = std::max<int64_t>(K, 1);
-    NR_REQUIRE(K <= kMaxPhases, NR_ERR_UNSUPPORTED,
-               "spmm_blocked: gathered table of %lld rows needs %lld column blocks (max %d) — "
-               "use the work-item kernel", (long long)span, (long long)K, kMaxPhases);
-    const int64_t width = (span + K - 1) / K;
-    n_phases = std::max<int>(n_phases, (int)K);
-    cl.cmin = cmin; cl.width = width; cl.K = K;
-    // Which rows a workgroup owns.  r01-r04: contiguous runs balanced by cost — fine while a row's length is
-    // independent of its id (the first synthetic twin shuffled the popularity ranks), but in real interaction data
-    // (and in the r05 twin, whose item popularity follows the real test split) popular items cluster in id: the
-    // run of hub rows then holds few rows and the runs of tail rows hit the accumulator cap (kRMax rows of ~8
-    // non-zeros = 0.7 of the cost target), which pushes the excess onto the other runs — the slowest workgroup of
-    // the item class carried 1.9x the mean cost and the pass took 50 us instead of 34.  r05: rows are DEALT —
-    // sorted by cost, each to the least-loaded workgroup that still has an accumulator (LPT) — so every
-    // workgroup gets the same cost whatever the numbering; the plan lists a workgroup's rows (row_of) and owns
-    // the (column, value) pairs in that order.  (The r01-r04 contiguous runs left the product in r06:
-    // profiles/r05_exp_entcost.txt has the A/B.)
-    const int64_t n_cl = cl.rb - cl.ra;
-    const int64_t nw = (int64_t)cl.wgs.size();
-    std::vector<std::vector<int32_t>> lists((size_t)nw);
-    {
-      NR_REQUIRE(n_cl <= nw * (int64_t)kRMax, NR_ERR_UNSUPPORTED,
-                 "spmm_blocked: %lld rows do not fit %zu workgroups x %d accumulators — use the work-item kernel",
-                 (long long)n_cl, cl.wgs.size(), kRMax);
-      std::vector<int32_t> by_cost((size_t)n_cl);
-      for (int64_t q = 0; q < n_cl; ++q) by_cost[(size_t)q] = (int32_t)(cl.ra + q);
-      std::stable_sort(by_cost.begin(), by_cost.end(), [&](int32_t x, int32_t y) {
-        return h_indptr[x + 1] - h_indptr[x] > h_indptr[y + 1] - h_indptr[y];
-      });
-      // min-heap of (cost so far, workgroup); a workgroup whose accumulators are all taken leaves the heap
-      typedef std::pair<int64_t, int> Load;
-      std::priority_queue<Load, std::vector<Load>, std::greater<Load>> heap;
-      for (int i = 0; i < (int)nw; ++i) heap.push(Load(0, i));
-      // rows that cannot be placed freely any more (as many rows left as free accumulators) are not an issue:
-      // every workgroup in the heap has a free accumulator and n_cl <= nw * kRMax
-      for (int32_t row : by_cost) {
-        Load top = heap.top();
-        heap.pop();
-        lists[(size_t)top.second].push_back(row);
-        top.first += row_cost(h_indptr[row + 1] - h_indptr[row]);
-        if ((int64_t)lists[(size_t)top.second].size() < kRMax) heap.push(top);
-      }
-    }
-    for (size_t wi = 0; wi < cl.wgs.size(); ++wi) {
-      const int w = cl.wgs[wi];
-      wg_rows[(size_t)w].swap(lists[wi]);
-    }
-  }
-  // run order: workgroup by workgroup; the packed (column, value) arrays follow it
-  std::vector<int32_t> row_of((size_t)n_rows);
-  std::vector<uint32_t> pk_src((size_t)n_rows), pk_dst((size_t)n_rows + 1, 0);
-  {
-    int64_t k = 0;
-    for (int w = 0; w < n_wg; ++w) {
-      wg_row0[(size_t)w] = (int32_t)k;
-      wg_nrows[(size_t)w] = (int32_t)wg_rows[(size_t)w].size();
-      for (int32_t row : wg_rows[(size_t)w]) {
-        row_of[(size_t)k] = row;
-        pk_src[(size_t)k] = (uint32_t)h_indptr[row];
-        pk_dst[(size_t)k + 1] = pk_dst[(size_t)k] + (uint32_t)(h_indptr[row + 1] - h_indptr[row]);
-        ++k;
-      }
-    }
-    NR_REQUIRE(k == n_rows, NR_ERR_ARG, "spmm_blocked: internal: %lld of %lld rows scheduled", (long long)k,
-               (long long)n_rows);
-  }
-  for (const ClassDesc& cl : classes) {
-    const int32_t cmin = cl.cmin;
-    const int64_t width = cl.width, K = cl.K;
-    for (size_t wi = 0; wi < cl.wgs.size(); ++wi) {
-      const int w = cl.wgs[wi];
-      wg_ent[w].assign((size_t)K, {});
-      wg_cmb[w].assign((size_t)K, {});
-      std::vector<int> pcount((size_t)K, 0);
-      for (size_t si = 0; si < wg_rows[(size_t)w].size(); ++si) {
-        const int64_t row = wg_rows[(size_t)w][si];
-        const int32_t slot = (int32_t)si;
-        // position of the row's first pair in the packed arrays
-        const int64_t shift = (int64_t)pk_dst[(size_t)wg_row0[(size_t)w] + si] - h_indptr[row];
-        int64_t t = h_indptr[row];
-        const int64_t te = h_indptr[row + 1];
-        if (t == te) wg_ent[w][0].push_back(HostEnt{slot, 0, (uint32_t)(t + shift), (int32_t)row});   // empty row
-        while (t < te) {
-          const int64_t k = ((int64_t)h_indices[t] - cmin) / width;
-          int64_t t2 = t + 1;
-          const int64_t col_end = cmin + (k + 1) * width;       // first column of the next block
-          while (t2 < te && h_indices[t2] < col_end) ++t2;
-          const int64_t len = t2 - t;
-          if (len <= kSeg) {
-            wg_ent[w][(size_t)k].push_back(HostEnt{slot, (int32_t)len, (uint32_t)(t + shift), (int32_t)row});
-          } else {
-            const int ns = (int)((len + kSeg - 1) / kSeg);
-            NR_REQUIRE(pcount[(size_t)k] + ns <= kPMax, NR_ERR_UNSUPPORTED,
-                       "spmm_blocked: more than %d hub segments in one workgroup phase — use the "
-                       "work-item kernel", kPMax);
-            const int first = kRMax + pcount[(size_t)k];
-            for (int sg = 0; sg < ns; ++sg)
-              wg_ent[w][(size_t)k].push_back(
-                  HostEnt{first + sg, (int32_t)std::min<int64_t>(kSeg, len - (int64_t)sg * kSeg),
-                          (uint32_t)(t + shift + (int64_t)sg * kSeg), (int32_t)row});
-            wg_cmb[w][(size_t)k].push_back(make_int4(slot, first, ns, (int)row));
-            pcount[(size_t)k] += ns;
-          }
-          t = t2;
-        }
-      }
-      for (auto& v : wg_ent[w])
-        std::stable_sort(v.begin(), v.end(), [](const HostEnt& a, const HostEnt& b) { return a.len > b.len; });
-    }
-  }
-  // flatten
-  std::vector<int32_t> ent_off((size_t)n_wg * (n_phases + 1), 0), cmb_off((size_t)n_wg * (n_phases + 1), 0);
-  std::vector<int4> ent, cmb;
-  for (int w = 0; w < n_wg; ++w) {
-    for (int k = 0; k <= n_phases; ++k) {
-      ent_off[(size_t)w * (n_phases + 1) + k] = (int32_t)ent.size();
-      cmb_off[(size_t)w * (n_phases + 1) + k] = (int32_t)cmb.size();
-      if (k < n_phases && (size_t)k < wg_ent[w].size()) {
-        for (const HostEnt& e : wg_ent[w][(size_t)k])
-          ent.push_back(make_int4(e.slot, e.len, (int)e.begin, e.owner));
-        for (const int4& cm : wg_cmb[w][(size_t)k]) cmb.push_back(cm);
-      }
-    }
-  }
-  std::vector<uint32_t> wg_nnz((size_t)n_wg * 2, 0);
-  int64_t nnz_cap = 0, ent_cap = 0;
-  for (int w = 0; w < n_wg; ++w) {
-    const int64_t b = pk_dst[(size_t)wg_row0[w]], en = pk_dst[(size_t)wg_row0[w] + (size_t)wg_nrows[w]];
-    wg_nnz[2 * (size_t)w] = (uint32_t)b;
-    wg_nnz[2 * (size_t)w + 1] = (uint32_t)(en - b);
-    nnz_cap = std::max(nnz_cap, en - b);
-    ent_cap = std::max<int64_t>(ent_cap, ent_off[(size_t)w * (n_phases + 1) + n_phases] -
-                                             ent_off[(size_t)w * (n_phases + 1)]);
-  }
+  nr_plan::Plan h;
+  rc = nr_plan::build_plan(h_indptr, h_indices, n_rows, opt, &h, &err);
+  NR_REQUIRE(rc == NR_OK, rc, "%s", err.msg.c_str());
+
   BlockedPlan* p = new (std::nothrow) BlockedPlan();
   NR_REQUIRE(p, NR_ERR_ARG, "spmm_blocked_plan_create: out of host memory");
-  p->nnz_cap = (int)std::min<int64_t>(nnz_cap, INT32_MAX / 16);
-  p->ent_cap = (int)std::min<int64_t>((ent_cap + 15) / 16 * 16, INT32_MAX / 32);
-  {
-    const char* off = getenv("NEUREC_SPMM_MASKED_FAST");     // "0": A/B against the general kernel
-    const bool on = d == 64 && kWaves == 16 && n_phases == 1 && !(off && off[0] == '0');
-    const size_t base = (size_t)kPMax * 256 + (size_t)p->ent_cap * 16;
-    p->colmask_ok = on && nnz_cap < ((int64_t)1 << 24) && n_rows < ((int64_t)1 << 24) &&
-                    base + (size_t)nnz_cap * 8 <= (size_t)kMaxLdsBytes;
-    p->wanted_ok = on && kSeg <= 255 && n_rows < ((int64_t)1 << 24);
-  }
-  std::vector<int4> w_ent, w_cmb;
-  std::vector<int32_t> w_ent_off((size_t)n_wg * 2, 0), w_cmb_off((size_t)n_wg * 2, 0);
-  p->w_ent_cap = 0;
-  p->w_nnz_cap = 0;
-  p->w_bitmap_words = 0;
-  if (p->wanted_ok) {
-    std::vector<int32_t> order((size_t)n_rows);
-    for (int64_t r = 0; r < n_rows; ++r) order[(size_t)r] = (int32_t)r;
-    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
-      return h_indptr[a + 1] - h_indptr[a] > h_indptr[b + 1] - h_indptr[b];
-    });
-    std::vector<std::vector<int4>> we((size_t)n_wg), wc((size_t)n_wg);
-    std::vector<int> wp((size_t)n_wg, 0);
-    for (int64_t k = 0; k < n_rows && p->wanted_ok; ++k) {
-      const int32_t row = order[(size_t)k];
-      const size_t w = (size_t)(k % n_wg);
-      const int64_t b = h_indptr[row], len = h_indptr[row + 1] - b;
-      if (len <= kSeg) {
-        we[w].push_back(make_int4(0, (int)len, (int)(uint32_t)b, row));
-      } else {
-        const int ns = (int)((len + kSeg - 1) / kSeg);
-        if (wp[w] + ns > kPMax) { p->wanted_ok = 0; break; }
-        for (int sg = 0; sg < ns; ++sg)
-          we[w].push_back(make_int4(kRMax + wp[w] + sg, (int)std::min<int64_t>(kSeg, len - (int64_t)sg * kSeg),
-                                    (int)(uint32_t)(b + (int64_t)sg * kSeg), row));
-        wc[w].push_back(make_int4(row, kRMax + wp[w], ns, 0));
-        wp[w] += ns;
-      }
-    }
-    for (int w = 0; w < n_wg && p->wanted_ok; ++w) {
-      w_ent_off[2 * (size_t)w] = (int32_t)w_ent.size();
-      w_cmb_off[2 * (size_t)w] = (int32_t)w_cmb.size();
-      w_ent.insert(w_ent.end(), we[(size_t)w].begin(), we[(size_t)w].end());
-      w_cmb.insert(w_cmb.end(), wc[(size_t)w].begin(), wc[(size_t)w].end());
-      w_ent_off[2 * (size_t)w + 1] = (int32_t)w_ent.size();
-      w_cmb_off[2 * (size_t)w + 1] = (int32_t)w_cmb.size();
-      p->w_ent_cap = std::max<int>(p->w_ent_cap, (int)we[(size_t)w].size());
-    }
-    p->w_ent_cap = (p->w_ent_cap + 15) / 16 * 16;
-    // LDS: partial slots + two descriptor lists + whatever is left for staged (column, value) pairs
-    // a bit per row for the batch form of the kernel, when the matrix is small enough to afford it
-    p->w_bitmap_words = n_rows <= 131072 ? (int)((n_rows + 127) / 128 * 4) : 0;
-    const int64_t left = (int64_t)kMaxLdsBytes - 256 - (int64_t)kPMax * 256 - 2 * (int64_t)p->w_ent_cap * 16 -
-                         (int64_t)p->w_bitmap_words * 4;
-    p->w_nnz_cap = (int)std::min<int64_t>(left / 8, (int64_t)1 << 22);
-    if (const char* cap = getenv("NEUREC_SPMM_WANTED_NNZ_CAP"))     // tests: force the chunked path
-      p->w_nnz_cap = std::min(p->w_nnz_cap, std::max(atoi(cap), 4 * kSeg));
-    if (p->w_nnz_cap < 4 * kSeg) p->wanted_ok = 0;
-  }
-  // wave-cooperative row-masked hop (spmm_wanted_wave_kernel): its own schedule — whole rows of <= 64
-  // non-zeros and CHUNKS of <= kChunk consecutive 64-segments of longer rows are the units, dealt to
-  // the workgroups by descending length.  NEUREC_SPMM_WANTED_WAVE=0 keeps the staged lane-group
-  // walker (A/B runs).
-  std::vector<int4> ww_ent, ww_hub, ww_lcmb;
-  std::vector<int32_t> ww_off((size_t)n_wg + 1, 0), ww_choff((size_t)n_wg + 1, 0), ww_lcoff((size_t)n_wg + 1, 0), ww_gch;
-  int64_t ww_segments = 0;
-  p->ww_ok = 0;
-  p->ww_ent_cap = 0;
-  p->ww_lds_slots = 0;
-  {
-    const char* off = getenv("NEUREC_SPMM_WANTED_WAVE");
-    const bool on = d == 64 && kWaves == 16 && kSeg <= 64 && n_rows <= 131072 * 4 && !(off && off[0] == '0');
-    if (on) {
-      constexpr int kChunk = 8;
-      // hub >= 0: chunk of a multi-chunk row (global partials); hub == -2: a one-chunk row of > 64
-      // non-zeros (segment sums in LDS); hub == -1: a whole row of <= 64
-      struct Unit { int64_t len; int32_t row; int hub, seg0, nseg; };
-      std::vector<Unit> units;
-      for (int64_t r = 0; r < n_rows; ++r) {
-        const int64_t len = h_indptr[r + 1] - h_indptr[r];
-        if (len <= kSeg) {
-          units.push_back(Unit{len, (int32_t)r, -1, 0, 0});
-          continue;
-        }
-        const int ns = (int)((len + kSeg - 1) / kSeg), nch = (ns + kChunk - 1) / kChunk;
-        if (nch == 1) {
-          units.push_back(Unit{len, (int32_t)r, -2, 0, ns});
-          continue;
-        }
-        const int hub = (int)ww_hub.size();
-        ww_hub.push_back(make_int4((int)r, (int)ww_segments, ns, nch));
-        for (int ch = 0; ch < nch; ++ch) {
-          const int s0 = ch * kChunk, s1 = std::min(ns, s0 + kChunk);
-          units.push_back(Unit{std::min<int64_t>(len - (int64_t)s0 * kSeg, (int64_t)(s1 - s0) * kSeg), (int32_t)r,
-                               hub, s0, s1 - s0});
-        }
-        ww_segments += ns;
-      }
-      std::stable_sort(units.begin(), units.end(), [](const Unit& a, const Unit& b) { return a.len > b.len; });
-      std::vector<std::vector<int4>> per((size_t)n_wg), perl((size_t)n_wg);
-      std::vector<std::vector<int32_t>> perch((size_t)n_wg);
-      std::vector<int> lds_used((size_t)n_wg, 0);
-      for (size_t k = 0; k < units.size(); ++k) {
-        const Unit& u = units[k];
-        const size_t w = k % (size_t)n_wg;
-        const int64_t b = h_indptr[u.row], len = h_indptr[u.row + 1] - b;
-        if (u.hub == -1) {
-          per[w].push_back(make_int4(0, (int)len, (int)(uint32_t)b, u.row));
-        } else if (u.hub == -2) {
-          perl[w].push_back(make_int4(u.row, lds_used[w], u.nseg, 0));
-          for (int sg = 0; sg < u.nseg; ++sg)
-            per[w].push_back(make_int4(-(1 + lds_used[w] + sg), (int)std::min<int64_t>(kSeg, len - (int64_t)sg * kSeg),
-                                       (int)(uint32_t)(b + (int64_t)sg * kSeg), u.row));
-          lds_used[w] += u.nseg;
-        } else {
-          for (int sg = u.seg0; sg < u.seg0 + u.nseg; ++sg)
-            per[w].push_back(make_int4(1 + ww_hub[(size_t)u.hub].y + sg,
-                                       (int)std::min<int64_t>(kSeg, len - (int64_t)sg * kSeg),
-                                       (int)(uint32_t)(b + (int64_t)sg * kSeg), u.row));
-          perch[w].push_back(u.hub);
-        }
-      }
-      p->ww_lds_slots = 0;
-      for (int w = 0; w < n_wg; ++w) {
-        ww_off[(size_t)w] = (int32_t)ww_ent.size();
-        ww_choff[(size_t)w] = (int32_t)ww_gch.size();
-        ww_lcoff[(size_t)w] = (int32_t)ww_lcmb.size();
-        ww_ent.insert(ww_ent.end(), per[(size_t)w].begin(), per[(size_t)w].end());
-        ww_gch.insert(ww_gch.end(), perch[(size_t)w].begin(), perch[(size_t)w].end());
-        ww_lcmb.insert(ww_lcmb.end(), perl[(size_t)w].begin(), perl[(size_t)w].end());
-        p->ww_ent_cap = std::max<int>(p->ww_ent_cap, (int)per[(size_t)w].size());
-        p->ww_lds_slots = std::max(p->ww_lds_slots, lds_used[(size_t)w]);
-      }
-      ww_off[(size_t)n_wg] = (int32_t)ww_ent.size();
-      ww_choff[(size_t)n_wg] = (int32_t)ww_gch.size();
-      ww_lcoff[(size_t)n_wg] = (int32_t)ww_lcmb.size();
-      p->ww_ent_cap = (p->ww_ent_cap + 15) / 16 * 16;
-      p->ww_ok = ww_segments < ((int64_t)1 << 30) &&
-                 (size_t)p->ww_lds_slots * 256 + (size_t)p->ww_ent_cap * 16 +
-                         (size_t)((n_rows + 127) / 128 * 16) + 1024 <= (size_t)kMaxLdsBytes;
-    }
-  }
-  p->n_rows = n_rows; p->nnz = nnz; p->n_wg = n_wg; p->n_phases = n_phases;
-  p->seg = kSeg; p->r_max = kRMax; p->p_max = kPMax; p->waves = kWaves; p->d = d;
-  p->n_ent = (int64_t)ent.size(); p->n_cmb = (int64_t)cmb.size();
-  char* q = (char*)d_plan_buf;
-  auto carve = [&](size_t bytes) { void* r = q; q += nr_align_up(bytes, 256); return r; };
-  p->ent = (int4*)carve(ent.size() * 16 + 16);
-  p->cmb = (int4*)carve(cmb.size() * 16 + 16);
-  p->wg_row0 = (int32_t*)carve((size_t)n_wg * 4);
-  p->wg_nrows = (int32_t*)carve((size_t)n_wg * 4);
-  p->row_of = (int32_t*)carve(row_of.size() * 4);
-  p->pk_src = (uint32_t*)carve(pk_src.size() * 4);
-  p->pk_dst = (uint32_t*)carve(pk_dst.size() * 4);
-  p->pk_idx = (int32_t*)carve((size_t)nnz * 4 + 4);
-  p->pk_val = (float*)carve((size_t)nnz * 4 + 4);
-  p->pk_from_idx = nullptr;
-  p->pk_from_val = nullptr;
-  p->wg_ent_off = (int32_t*)carve(ent_off.size() * 4);
-  p->wg_cmb_off = (int32_t*)carve(cmb_off.size() * 4);
-  p->wg_nnz = (uint32_t*)carve(wg_nnz.size() * 4);
-  p->w_ent = (int4*)carve(w_ent.size() * 16 + 16);
-  p->w_cmb = (int4*)carve(w_cmb.size() * 16 + 16);
-  p->w_ent_off = (int32_t*)carve(w_ent_off.size() * 4);
-  p->w_cmb_off = (int32_t*)carve(w_cmb_off.size() * 4);
-  p->ww_off = p->ww_choff = p->ww_gch = p->ww_lcoff = nullptr; p->ww_ent = p->ww_hub = p->ww_lcmb = nullptr;
-  p->ww_part = nullptr; p->ww_cnt = nullptr;
-  if (p->ww_ok) {
-    p->ww_off = (int32_t*)carve(ww_off.size() * 4);
-    p->ww_choff = (int32_t*)carve(ww_choff.size() * 4);
-    p->ww_ent = (int4*)carve(ww_ent.size() * 16 + 16);
-    p->ww_gch = (int32_t*)carve(ww_gch.size() * 4 + 4);
-    p->ww_hub = (int4*)carve(ww_hub.size() * 16 + 16);
-    p->ww_lcoff = (int32_t*)carve(ww_lcoff.size() * 4);
-    p->ww_lcmb = (int4*)carve(ww_lcmb.size() * 16 + 16);
-    p->ww_part = (float*)carve((size_t)ww_segments * 256 + 256);
-    p->ww_cnt = (unsigned*)carve(ww_hub.size() * 4 + 4);
-  }
-  if ((size_t)(q - (char*)d_plan_buf) > plan_bytes) {
+  p->n_rows = n_rows; p->nnz = nnz; p->n_wg = h.n_wg; p->n_phases = h.n_phases;
+  p->seg = opt.seg; p->r_max = opt.r_max; p->p_max = opt.p_max; p->waves = opt.waves; p->d = d;
+  p->n_ent = (int64_t)h.ent.size(); p->n_cmb = (int64_t)h.cmb.size();
+  p->nnz_cap = h.nnz_cap; p->ent_cap = h.ent_cap; p->colmask_ok = h.colmask_ok;
+  p->wanted_ok = h.wanted_ok; p->w_ent_cap = h.w_ent_cap; p->w_nnz_cap = h.w_nnz_cap; p->w_bitmap_words = h.w_bitmap_words;
+  p->ww_ok = h.ww_ok; p->ww_ent_cap = h.ww_ent_cap; p->ww_lds_slots = h.ww_lds_slots;
+  std::vector<nr_plan::Section> sections = nr_plan::plan_sections(*p, h);
+  const size_t used = nr_plan::carve_sections(&sections, d_plan_buf);
+  if (used > plan_bytes) {
     delete p;
-    nrhip_set_error("spmm_blocked_plan_create: plan needs %zu bytes, buffer has %zu",
-                    (size_t)(q - (char*)d_plan_buf), plan_bytes);
+    nrhip_set_error("spmm_blocked_plan_create: plan needs %zu bytes, buffer has %zu", used, plan_bytes);
     return NR_ERR_WORKSPACE;
   }
   hipStream_t st = (hipStream_t)stream;
   hipError_t e = hipSuccess;
-  auto up = [&](void* dst, const void* src, size_t n) {
-    if (n && e == hipSuccess) e = hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, st);
-  };
-  up(p->ent, ent.data(), ent.size() * 16);
-  up(p->cmb, cmb.data(), cmb.size() * 16);
-  up(p->wg_row0, wg_row0.data(), wg_row0.size() * 4);
-  up(p->wg_nrows, wg_nrows.data(), wg_nrows.size() * 4);
-  up(p->row_of, row_of.data(), row_of.size() * 4);
-  up(p->pk_src, pk_src.data(), pk_src.size() * 4);
-  up(p->pk_dst, pk_dst.data(), pk_dst.size() * 4);
-  up(p->wg_ent_off, ent_off.data(), ent_off.size() * 4);
-  up(p->wg_cmb_off, cmb_off.data(), cmb_off.size() * 4);
-  up(p->wg_nnz, wg_nnz.data(), wg_nnz.size() * 4);
-  up(p->w_ent, w_ent.data(), w_ent.size() * 16);
-  up(p->w_cmb, w_cmb.data(), w_cmb.size() * 16);
-  up(p->w_ent_off, w_ent_off.data(), w_ent_off.size() * 4);
-  up(p->w_cmb_off, w_cmb_off.data(), w_cmb_off.size() * 4);
-  if (p->ww_ok) {
-    up(p->ww_off, ww_off.data(), ww_off.size() * 4);
-    up(p->ww_choff, ww_choff.data(), ww_choff.size() * 4);
-    up(p->ww_ent, ww_ent.data(), ww_ent.size() * 16);
-    up(p->ww_gch, ww_gch.data(), ww_gch.size() * 4);
-    up(p->ww_hub, ww_hub.data(), ww_hub.size() * 16);
-    up(p->ww_lcoff, ww_lcoff.data(), ww_lcoff.size() * 4);
-    up(p->ww_lcmb, ww_lcmb.data(), ww_lcmb.size() * 16);
-    if (e == hipSuccess) e = hipMemsetAsync(p->ww_cnt, 0, ww_hub.size() * 4 + 4, st);
+  for (const nr_plan::Section& s : sections) {
+    if (e != hipSuccess) break;
+    if (s.src && s.bytes) e = hipMemcpyAsync(s.addr, s.src, s.bytes, hipMemcpyHostToDevice, st);
+    else if (s.zero) e = hipMemsetAsync(s.addr, 0, s.bytes + s.pad, st);
   }
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  const int lds = (kRMax + kPMax) * kD * 4 + kRMax * 4;           // accumulators + the workgroup's row list
-  auto allow = [&](const void* fn) {
-    if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  };
-#define NR_ALLOW(DD)                                                                             \
-  allow((const void*)spmm_blocked_kernel<false, 16, 8, DD>); allow((const void*)spmm_blocked_kernel<true, 16, 8, DD>); \
-  allow((const void*)spmm_blocked_kernel<false, 16, 4, DD>); allow((const void*)spmm_blocked_kernel<true, 16, 4, DD>); \
-  allow((const void*)spmm_blocked_kernel<false, 8, 8, DD>); allow((const void*)spmm_blocked_kernel<true, 8, 8, DD>);   \
-  allow((const void*)spmm_blocked_kernel<false, 8, 4, DD>); allow((const void*)spmm_blocked_kernel<true, 8, 4, DD>)
-  if (d == 16) { NR_ALLOW(16); } else if (d == 32) { NR_ALLOW(32); }
-  else if (d == 64) {
-    NR_ALLOW(64);
-    allow((const void*)spmm_blocked_kernel<false, 16, 8, 64, true>);
-  }
-  else if (d == 128) { NR_ALLOW(128); } else { NR_ALLOW(256); }
-#undef NR_ALLOW
-  if (p->wanted_ok && e == hipSuccess)
-    e = hipFuncSetAttribute((const void*)spmm_wanted_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)wanted_lds_bytes(p));
-  if (p->ww_ok && e == hipSuccess)
-    e = hipFuncSetAttribute((const void*)spmm_wanted_wave_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)ww_lds_bytes(p));
-  if (p->colmask_ok)
-    for (const void* fn : {(const void*)spmm_staged_masked_kernel<true, false>,
-                           (const void*)spmm_staged_masked_kernel<false, true>,
-                           (const void*)spmm_staged_masked_kernel<true, true>})
-      if (e == hipSuccess)
-        e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)colmask_lds_bytes(p));
+  if (e == hipSuccess) e = allow_plan_lds(p);
   if (e != hipSuccess) {
     delete p;
     nrhip_set_error("spmm_blocked_plan_create: %s", hipGetErrorString(e));
