@@ -527,6 +527,36 @@ int nrhip_spmm_blocked_wanted_batch(const void* plan, const int32_t* d_indices, 
 /* 0: no wanted-rows schedule, 1: flag form only, 2: flag and batch forms (not status codes) */
 int nrhip_spmm_plan_has_wanted(const void* plan, int d);
 int nrhip_spmm_blocked_has_wanted(const void* blocked_plan);
+/* The batch-rows hop from a per-batch work list made an epoch ahead (csrc/spmm_wanted_plan.h has the layout).
+ * A batch is no run-time surprise: nrhip_bpr_plan leaves every batch's distinct rows, sorted, for the whole epoch
+ * stream.  _epoch_plan turns them into one list of wave-sized items per batch (records of 16 bytes, *stride per
+ * batch) in ONE launch without a host read; _wanted_planned is nrhip_spmm_csr_wanted_batch run from the batch's own
+ * records d_batch_sched = d_sched + k * stride * 16: no bit set, no descriptor scan, one round per workgroup, the
+ * same additions in the same order.  _has_wanted_planned: 1 when the matrix has it (d = 64, <= 2^19 rows,
+ * NEUREC_SPMM_WANTED_PLANNED != 0).  d_plans: 3 * batch keys per batch, the last batch last_len triplets;
+ * 3 * batch <= 16384.  d_indptr: the matrix's row offsets on the device. */
+int nrhip_spmm_plan_has_wanted_planned(const void* plan, int d);
+int nrhip_spmm_blocked_has_wanted_planned(const void* blocked_plan);
+int nrhip_spmm_wanted_epoch_plan_bytes(const void* plan, int d, int batch, int64_t n_batches, size_t* bytes,
+                                       int* stride);
+int nrhip_spmm_blocked_wanted_epoch_plan_bytes(const void* blocked_plan, int batch, int64_t n_batches, size_t* bytes,
+                                               int* stride);
+int nrhip_spmm_wanted_epoch_plan(const void* plan, int d, const int64_t* d_indptr, const uint64_t* d_plans, int batch,
+                                 int64_t n_batches, int last_len, void* d_sched, size_t sched_bytes, void* stream);
+int nrhip_spmm_blocked_wanted_epoch_plan(const void* blocked_plan, const int64_t* d_indptr, const uint64_t* d_plans,
+                                         int batch, int64_t n_batches, int last_len, void* d_sched, size_t sched_bytes,
+                                         void* stream);
+int nrhip_spmm_csr_wanted_planned(const void* plan, const int32_t* d_indices, const float* d_vals, const float* d_X,
+                                  int d, const float* d_sum_in, const float* d_layer_a, const float* d_layer_b,
+                                  float* d_sum_out, const int32_t* d_users, const int32_t* d_pos, const int32_t* d_neg,
+                                  int batch, int n_users, uint8_t* d_row_flag, int32_t* d_rows_out,
+                                  const void* d_batch_sched, int stride, void* stream);
+int nrhip_spmm_blocked_wanted_planned(const void* blocked_plan, const int32_t* d_indices, const float* d_vals,
+                                      const float* d_X, const float* d_sum_in, const float* d_layer_a,
+                                      const float* d_layer_b, float* d_sum_out, const int32_t* d_users,
+                                      const int32_t* d_pos, const int32_t* d_neg, int batch, int n_users,
+                                      uint8_t* d_row_flag, int32_t* d_rows_out, const void* d_batch_sched, int stride,
+                                      void* stream);
 
 /* Chunked propagation hop of the row-sharded engine (neurec_amd/sharded.py; LightGCN.py:132-149 with the operand
  * arriving in rank-ordered chunks — SURVEY 8e "overlap layer-k comm with layer-k local SpMM").  One launch per
@@ -611,6 +641,11 @@ int nrhip_lightgcn_ctx_destroy(void* ctx);
 int nrhip_lightgcn_step(void* ctx, const int32_t* d_users, const int32_t* d_pos,
                         const int32_t* d_neg, int batch, const uint64_t* d_plan, float alpha,
                         float beta1, float beta2, float eps, float* d_loss2, void* stream);
+/* The same step with the batch-rows hop run from the batch's records of an nrhip_spmm_wanted_epoch_plan output
+ * (d_hop_sched, hop_stride records; the context's forward matrix must have nrhip_spmm_plan_has_wanted_planned). */
+int nrhip_lightgcn_step_planned(void* ctx, const int32_t* d_users, const int32_t* d_pos, const int32_t* d_neg,
+                                int batch, const uint64_t* d_plan, const void* d_hop_sched, int hop_stride,
+                                float alpha, float beta1, float beta2, float eps, float* d_loss2, void* stream);
 
 /* Column-sharded tables (LightGCN.py:132-166 when every rank holds d of the D embedding columns — the propagation,
  * the gradient rows and ApplyAdam are column-wise, so the only quantity that needs all columns is the head's inner
@@ -619,6 +654,9 @@ int nrhip_lightgcn_step(void* ctx, const int32_t* d_users, const int32_t* d_pos,
  * order; _bwd: head with the summed d_given, backward hops, ApplyAdam.  Every rank steps on the SAME global batch. */
 int nrhip_lightgcn_step_colshard_fwd(void* ctx, const int32_t* d_users, const int32_t* d_pos, const int32_t* d_neg,
                                      int batch, float* d_partials, void* stream);
+int nrhip_lightgcn_step_colshard_fwd_planned(void* ctx, const int32_t* d_users, const int32_t* d_pos,
+                                             const int32_t* d_neg, int batch, const void* d_hop_sched, int hop_stride,
+                                             float* d_partials, void* stream);
 int nrhip_lightgcn_step_colshard_bwd(void* ctx, const int32_t* d_users, const int32_t* d_pos, const int32_t* d_neg,
                                      int batch, const uint64_t* d_plan, const float* d_given, float alpha,
                                      float beta1, float beta2, float eps, float* d_loss2, void* stream);

@@ -209,6 +209,8 @@ SIGNATURES = {
     "nrhip_mf_steps": [p, p, p, p, i64, i32, p, i32, p, f32, f32, f32, p, p, p],
     "nrhip_loss_reduce_steps": [p, i32, i32, i32, f32, p, p],
     "nrhip_lightgcn_step_colshard_fwd": [p, p, p, p, i32, p, p],
+    "nrhip_lightgcn_step_colshard_fwd_planned": [p, p, p, p, i32, p, i32, p, p],
+    "nrhip_lightgcn_step_planned": [p, p, p, p, i32, p, p, i32, f32, f32, f32, f32, p, p],
     "nrhip_lightgcn_step_colshard_bwd": [p, p, p, p, i32, p, p, f32, f32, f32, f32, p, p],
     "nrhip_lightgcn_partial_dots": [p, p, i32, i32, i32, p, p, p, i32, p, p],
     "nrhip_partials_sum": [p, i32, i32, p, p],
@@ -261,6 +263,14 @@ SIGNATURES = {
     "nrhip_spmm_plan_has_blocked": [p, i32],
     "nrhip_spmm_plan_has_wanted": [p, i32],
     "nrhip_spmm_blocked_has_wanted": [p],
+    "nrhip_spmm_plan_has_wanted_planned": [p, i32],
+    "nrhip_spmm_blocked_has_wanted_planned": [p],
+    "nrhip_spmm_wanted_epoch_plan_bytes": [p, i32, i32, i64, psz, C.POINTER(i32)],
+    "nrhip_spmm_blocked_wanted_epoch_plan_bytes": [p, i32, i64, psz, C.POINTER(i32)],
+    "nrhip_spmm_wanted_epoch_plan": [p, i32, p, p, i32, i64, i32, p, sz, p],
+    "nrhip_spmm_blocked_wanted_epoch_plan": [p, p, p, i32, i64, i32, p, sz, p],
+    "nrhip_spmm_csr_wanted_planned": [p, p, p, p, i32, p, p, p, p, p, p, p, i32, i32, p, p, p, i32, p],
+    "nrhip_spmm_blocked_wanted_planned": [p, p, p, p, p, p, p, p, p, p, p, i32, i32, p, p, p, i32, p],
     "nrhip_spmm_csr_wanted_layers": [p, p, p, p, i32, p, p, p, p, p, p],
     "nrhip_spmm_blocked_wanted_layers": [p, p, p, p, p, p, p, p, p, p],
     "nrhip_spmm_csr_wanted_batch": [p, p, p, p, i32, p, p, p, p, p, p, p, i32, i32, p, p, p],

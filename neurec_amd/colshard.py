@@ -62,7 +62,8 @@ class ColumnShardedLightGCN:
         if B > self.max_batch:
             raise ValueError("batch larger than max_batch")
         ctx, n = self.local._ctx, 3 * B
-        ctx.lightgcn_step_colshard_fwd(users, pos, neg, self._parts)
+        hop = self.local._hop.for_batch(plan, B) if self.local._hop is not None else None
+        ctx.lightgcn_step_colshard_fwd(users, pos, neg, self._parts, hop=hop)
         if self.comm.live and self.world == self.comm.world:
             allp = torch.empty((self.world, n), dtype=torch.float32, device=self._parts.device)
             self.comm.all_gather_rows(self._parts[:n], allp)            # the step's ONE exchange: 12 B per triplet and rank

@@ -60,6 +60,18 @@ extern "C" int nrhip_spmm_blocked_wanted_batch(const void* plan, const int32_t* 
                                                const int32_t* d_neg, int batch, int n_users,
                                                uint8_t* d_row_flag, int32_t* d_rows_out, void* stream);
 extern "C" int nrhip_spmm_blocked_has_wanted(const void* plan);
+extern "C" int nrhip_spmm_blocked_has_wanted_planned(const void* plan);
+extern "C" int nrhip_spmm_blocked_wanted_epoch_plan_bytes(const void* plan, int batch, int64_t n_batches, size_t* bytes,
+                                                          int* stride);
+extern "C" int nrhip_spmm_blocked_wanted_epoch_plan(const void* plan, const int64_t* d_indptr, const uint64_t* d_plans,
+                                                    int batch, int64_t n_batches, int last_len, void* d_sched,
+                                                    size_t sched_bytes, void* stream);
+extern "C" int nrhip_spmm_blocked_wanted_planned(const void* plan, const int32_t* d_indices, const float* d_vals,
+                                                 const float* d_X, const float* d_sum_in, const float* d_layer_a,
+                                                 const float* d_layer_b, float* d_sum_out, const int32_t* d_users,
+                                                 const int32_t* d_pos, const int32_t* d_neg, int batch, int n_users,
+                                                 uint8_t* d_row_flag, int32_t* d_rows_out, const void* d_batch_sched,
+                                                 int stride, void* stream);
 extern "C" int nrhip_spmm_blocked_adam(const void* plan, const int32_t* d_indices,
                                        const float* d_vals, const float* d_X, float* d_addend,
                                        float* d_grad_b, float* d_var, float* d_m, float* d_v,
@@ -933,6 +945,41 @@ int nrhip_spmm_csr_wanted_batch(const void* plan, const int32_t* d_indices, cons
   return nrhip_spmm_blocked_wanted_batch(p->blocked[blocked_slot(64)], d_indices, d_vals, d_X, d_sum_in,
                                          d_layer_a, d_layer_b, d_sum_out, d_users, d_pos, d_neg, batch,
                                          n_users, d_row_flag, d_rows_out, stream);
+}
+
+// the planned form of the batch-rows hop (spmm_wanted_plan.h) behind the matrix handle
+int nrhip_spmm_plan_has_wanted_planned(const void* plan, int d) {
+  if (!plan || d != 64) return 0;
+  const SpmmPlan* p = (const SpmmPlan*)plan;
+  return p->blocked[blocked_slot(64)] ? nrhip_spmm_blocked_has_wanted_planned(p->blocked[blocked_slot(64)]) : 0;
+}
+
+int nrhip_spmm_wanted_epoch_plan_bytes(const void* plan, int d, int batch, int64_t n_batches, size_t* bytes,
+                                       int* stride) {
+  NR_REQUIRE(nrhip_spmm_plan_has_wanted_planned(plan, d), NR_ERR_UNSUPPORTED,
+             "spmm_wanted_epoch_plan_bytes: no planned batch-rows hop for this matrix and width");
+  return nrhip_spmm_blocked_wanted_epoch_plan_bytes(((const SpmmPlan*)plan)->blocked[blocked_slot(64)], batch, n_batches,
+                                                    bytes, stride);
+}
+
+int nrhip_spmm_wanted_epoch_plan(const void* plan, int d, const int64_t* d_indptr, const uint64_t* d_plans, int batch,
+                                 int64_t n_batches, int last_len, void* d_sched, size_t sched_bytes, void* stream) {
+  NR_REQUIRE(nrhip_spmm_plan_has_wanted_planned(plan, d), NR_ERR_UNSUPPORTED,
+             "spmm_wanted_epoch_plan: no planned batch-rows hop for this matrix and width");
+  return nrhip_spmm_blocked_wanted_epoch_plan(((const SpmmPlan*)plan)->blocked[blocked_slot(64)], d_indptr, d_plans,
+                                              batch, n_batches, last_len, d_sched, sched_bytes, stream);
+}
+
+int nrhip_spmm_csr_wanted_planned(const void* plan, const int32_t* d_indices, const float* d_vals, const float* d_X,
+                                  int d, const float* d_sum_in, const float* d_layer_a, const float* d_layer_b,
+                                  float* d_sum_out, const int32_t* d_users, const int32_t* d_pos, const int32_t* d_neg,
+                                  int batch, int n_users, uint8_t* d_row_flag, int32_t* d_rows_out,
+                                  const void* d_batch_sched, int stride, void* stream) {
+  NR_REQUIRE(nrhip_spmm_plan_has_wanted_planned(plan, d), NR_ERR_UNSUPPORTED,
+             "spmm_csr_wanted_planned: no planned batch-rows hop for this matrix and width");
+  return nrhip_spmm_blocked_wanted_planned(((const SpmmPlan*)plan)->blocked[blocked_slot(64)], d_indices, d_vals, d_X,
+                                           d_sum_in, d_layer_a, d_layer_b, d_sum_out, d_users, d_pos, d_neg, batch,
+                                           n_users, d_row_flag, d_rows_out, d_batch_sched, stride, stream);
 }
 
 int nrhip_spmm_plan_has_wanted(const void* plan, int d) {

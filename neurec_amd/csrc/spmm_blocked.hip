@@ -28,6 +28,7 @@
 // Epilogue as in spmm.hip: y += addend, sum_out = sum_in + y.
 #include "nr_common.h"
 #include "spmm_blocked_plan.h"
+#include "spmm_wanted_plan.h"
 #include <algorithm>
 #include <new>
 #include <cstdlib>
@@ -55,6 +56,8 @@ struct BlockedPlan : nr_plan::PlanArrays<int4> {
   int wanted_ok, w_ent_cap, w_nnz_cap, w_bitmap_words;      // staged wanted-rows schedule (row-masked hop)
   int ww_ok, ww_ent_cap;                                    // wave-cooperative row-masked hop
   int ww_lds_slots;      // LDS partial slots per workgroup
+  int wp_ok, n_hubs;     // planned row-masked hop (spmm_wanted_plan.h): allowed; records in ww_hub
+  nr_wplan::SlotProfile wp_profile;
 };
 
 
@@ -735,6 +738,140 @@ __device__ unsigned long long g_ww_dbg[256 * 8];
 #define NR_WW_STAMP_END(i)
 #endif
 
+// What the two wave-cooperative kernels (a schedule walked per workgroup / a per-batch item list) share.
+// ww_sublist_sum: one sub-list of <= 64 pairs by one wave — lane L holds pair L (col, val; lanes past the end
+// hold column 0); the ordered sum comes back in every lane for its column c.  between(): loads the caller
+// wants in flight with the gathers.
+template <class Between>
+__device__ __forceinline__ float4 ww_sublist_sum(int col, float val, int len, const float4* __restrict__ X, int c,
+                                                 int g, Between between) {
+  constexpr int RS = 16;
+  const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 x[16];
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    const int cj = __shfl(col, (g << 4) | j, NR_WAVE);           // lanes past the end hold column 0
+    x[j] = X[(int64_t)cj * RS + c];
+  }
+  between();
+  // products first (pair j of this lane group: value broadcast from lane 16g + j), in place
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    const float aj = __shfl(val, (g << 4) | j, NR_WAVE);
+    x[j] = make_float4(__fmul_rn(aj, x[j].x), __fmul_rn(aj, x[j].y), __fmul_rn(aj, x[j].z), __fmul_rn(aj, x[j].w));
+  }
+  float4 acc = zero, carry = zero;
+#pragma unroll
+  for (int gg = 0; gg < 4; ++gg) {
+    if (gg * 16 < len) {                                         // wave-uniform
+      if (g == gg) {
+        acc = carry;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+          const float4 t = make_float4(__fadd_rn(acc.x, x[j].x), __fadd_rn(acc.y, x[j].y),
+                                       __fadd_rn(acc.z, x[j].z), __fadd_rn(acc.w, x[j].w));
+          if (gg * 16 + j < len) acc = t;
+        }
+      }
+      const int src = (gg << 4) | c;
+      carry = make_float4(__shfl(acc.x, src, NR_WAVE), __shfl(acc.y, src, NR_WAVE),
+                          __shfl(acc.z, src, NR_WAVE), __shfl(acc.w, src, NR_WAVE));
+    }
+  }
+  return carry;
+}
+
+// the row's epilogue operands ride with the gathers (requested after the sum they would be one more memory
+// round trip per sub-list); rows that end in a partial slot read element 0
+struct WwPre { float4 si, a, b; };
+__device__ __forceinline__ WwPre ww_prefetch(const WantedEpi& ep, int64_t oe) {
+  const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+  WwPre p{zero, zero, zero};                                      // (an addend is read late: 128 VGPRs)
+  if (ep.sum_out) {
+    p.si = ep.sum_in[oe];
+    if (ep.chain.a) p.a = ep.chain.a[oe];
+    if (ep.chain.b) p.b = ep.chain.b[oe];
+  }
+  return p;
+}
+
+// lane group 0 puts a sub-list's sum where it belongs: slot == 0 the row itself (masked_row_out on the
+// prefetched operands), slot < 0 an LDS partial (lds_dst: its 16 float4), slot > 0 global partial slot - 1
+__device__ __forceinline__ void ww_sublist_out(float4 carry, int slot, int64_t o, int c, const WwPre& pre,
+                                               const WantedEpi& ep, float4* lds_dst, float* ww_part) {
+  if (slot == 0) {
+    float4 y = carry;
+    if (ep.addend) {
+      const float4 pre_add = ep.addend[o];
+      y = make_float4(__fadd_rn(y.x, pre_add.x), __fadd_rn(y.y, pre_add.y), __fadd_rn(y.z, pre_add.z),
+                      __fadd_rn(y.w, pre_add.w));
+    }
+    if (ep.Y) ep.Y[o] = y;
+    if (ep.sum_out) {
+      float4 si = pre.si;
+      if (ep.chain.a)
+        si = make_float4(__fadd_rn(si.x, pre.a.x), __fadd_rn(si.y, pre.a.y), __fadd_rn(si.z, pre.a.z),
+                         __fadd_rn(si.w, pre.a.w));
+      if (ep.chain.b)
+        si = make_float4(__fadd_rn(si.x, pre.b.x), __fadd_rn(si.y, pre.b.y), __fadd_rn(si.z, pre.b.z),
+                         __fadd_rn(si.w, pre.b.w));
+      ep.sum_out[o] = make_float4(__fadd_rn(si.x, y.x), __fadd_rn(si.y, y.y), __fadd_rn(si.z, y.z),
+                                  __fadd_rn(si.w, y.w));
+    }
+  } else if (slot < 0) {                                       // a segment of a one-chunk row: LDS
+    lds_dst[c] = carry;
+  } else {                                                     // a segment of a multi-chunk row: global,
+    float* mine = ww_part + (size_t)(slot - 1) * 64 + c * 4;   // agent scope (written through)
+    __hip_atomic_store(mine + 0, carry.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(mine + 1, carry.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(mine + 2, carry.z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(mine + 3, carry.w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// a wave reports one finished chunk of hub `hub` (hd: {row, first partial slot, segments, chunks}); the wave
+// that finishes the row last adds all its segment sums, 16 at a time in flight, in segment order
+__device__ __forceinline__ void ww_chunk_done(int hub, const int4 hd, unsigned* ww_cnt, const float* ww_part,
+                                              const WantedEpi& ep, int lane, int c, int g) {
+  constexpr int RS = 16;
+  unsigned old = 0;
+  if (lane == 0) old = __hip_atomic_fetch_add(&ww_cnt[hub], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  old = __builtin_amdgcn_readfirstlane(old);
+  if (old != (unsigned)hd.w - 1u) return;                      // another chunk of the row is still out
+  float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int s0 = 0; s0 < hd.z; s0 += 16) {
+    float4 q[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const float* qp = ww_part + ((size_t)hd.y + min(s0 + j, hd.z - 1)) * 64 + c * 4;
+      q[j].x = __hip_atomic_load(qp + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      q[j].y = __hip_atomic_load(qp + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      q[j].z = __hip_atomic_load(qp + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      q[j].w = __hip_atomic_load(qp + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+      if (s0 + j < hd.z)
+        sum = make_float4(__fadd_rn(sum.x, q[j].x), __fadd_rn(sum.y, q[j].y), __fadd_rn(sum.z, q[j].z),
+                          __fadd_rn(sum.w, q[j].w));
+  }
+  if (g == 0)
+    masked_row_out(sum, (int64_t)hd.x * RS + c, ep.addend, true, ep.Y, ep.sum_in, ep.sum_out, &ep.chain);
+  if (lane == 0) __hip_atomic_store(&ww_cnt[hub], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-armed
+}
+
+// the batch's rows published for the later kernels of the step: a contiguous piece of the 3 * batch list
+// positions per workgroup
+__device__ __forceinline__ void ww_publish_batch(const BatchLists& bl, int wg, int n_wg, int tid) {
+  const int total = 3 * bl.batch, per = (total + n_wg - 1) / n_wg;
+  for (int i = wg * per + tid; i < min(total, (wg + 1) * per); i += 16 * NR_WAVE) {
+    const int which = i / bl.batch, b = i - which * bl.batch;
+    const int row = which == 0 ? bl.users[b] : bl.n_users + (which == 1 ? bl.pos[b] : bl.neg[b]);
+    bl.row_flag[row] = 1;
+    if (bl.rows_out) bl.rows_out[i] = row;
+  }
+}
+
 __global__ __launch_bounds__(16 * NR_WAVE) void spmm_wanted_wave_kernel(
     const int32_t* __restrict__ ww_off, const int32_t* __restrict__ ww_choff,
     const int4* __restrict__ ww_ent, const int32_t* __restrict__ ww_gch, const int4* __restrict__ ww_hub,
@@ -770,14 +907,7 @@ __global__ __launch_bounds__(16 * NR_WAVE) void spmm_wanted_wave_kernel(
       if (p >= 0) atomicOr(&s_bits[rp >> 5], 1u << (rp & 31));
       if (q >= 0) atomicOr(&s_bits[rq >> 5], 1u << (rq & 31));
     }
-    // publishing is shared out: a contiguous piece of the 3 * batch list positions per workgroup
-    const int total = 3 * bl.batch, per = (total + (int)gridDim.x - 1) / (int)gridDim.x;
-    for (int i = wg * per + tid; i < min(total, (wg + 1) * per); i += 16 * NR_WAVE) {
-      const int which = i / bl.batch, b = i - which * bl.batch;
-      const int row = which == 0 ? bl.users[b] : bl.n_users + (which == 1 ? bl.pos[b] : bl.neg[b]);
-      bl.row_flag[row] = 1;
-      if (bl.rows_out) bl.rows_out[i] = row;
-    }
+    ww_publish_batch(bl, wg, (int)gridDim.x, tid);
   }
   __syncthreads();
   auto is_wanted = [&](int row) -> bool {
@@ -807,87 +937,25 @@ __global__ __launch_bounds__(16 * NR_WAVE) void spmm_wanted_wave_kernel(
   }
   while (k < n) {
     const int len = e.y, slot = e.x, row = e.w;
-    float4 x[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const int cj = __shfl(col, (g << 4) | j, NR_WAVE);           // lanes past the end hold column 0
-      x[j] = X[(int64_t)cj * RS + c];
-    }
-    // the row's epilogue operands ride with the gathers (requested after the sum they would be one
-    // more memory round trip per sub-list); rows that end in a partial slot read element 0
     const int64_t o = (int64_t)row * RS + c;
-    const int64_t oe = slot == 0 ? o : (int64_t)c;
-    float4 pre_si = zero, pre_a = zero, pre_b = zero;               // (an addend is read late: 128 VGPRs)
-    if (ep.sum_out) {
-      pre_si = ep.sum_in[oe];
-      if (ep.chain.a) pre_a = ep.chain.a[oe];
-      if (ep.chain.b) pre_b = ep.chain.b[oe];
-    }
+    WwPre pre;
     const int kn = k + 16;
     int4 en = zero_int4();
     int coln = 0;
     float valn = 0.f;
-    if (kn < n) {
-      en = s_want[kn];
-      if (lane < en.y) {
-        coln = indices[(uint32_t)en.z + lane];
-        valn = vals[(uint32_t)en.z + lane];
-      }
-    }
-    // products first (pair j of this lane group: value broadcast from lane 16g + j), in place
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const float aj = __shfl(val, (g << 4) | j, NR_WAVE);
-      x[j] = make_float4(__fmul_rn(aj, x[j].x), __fmul_rn(aj, x[j].y), __fmul_rn(aj, x[j].z), __fmul_rn(aj, x[j].w));
-    }
-    float4 acc = zero, carry = zero;
-#pragma unroll
-    for (int gg = 0; gg < 4; ++gg) {
-      if (gg * 16 < len) {                                         // wave-uniform
-        if (g == gg) {
-          acc = carry;
-#pragma unroll
-          for (int j = 0; j < 16; ++j) {
-            const float4 t = make_float4(__fadd_rn(acc.x, x[j].x), __fadd_rn(acc.y, x[j].y),
-                                         __fadd_rn(acc.z, x[j].z), __fadd_rn(acc.w, x[j].w));
-            if (gg * 16 + j < len) acc = t;
-          }
+    // the next sub-list's pairs are requested while this one's gathers are in flight
+    const float4 carry = ww_sublist_sum(col, val, len, X, c, g, [&]() {
+      pre = ww_prefetch(ep, slot == 0 ? o : (int64_t)c);
+      if (kn < n) {
+        en = s_want[kn];
+        if (lane < en.y) {
+          coln = indices[(uint32_t)en.z + lane];
+          valn = vals[(uint32_t)en.z + lane];
         }
-        const int src = (gg << 4) | c;
-        carry = make_float4(__shfl(acc.x, src, NR_WAVE), __shfl(acc.y, src, NR_WAVE),
-                            __shfl(acc.z, src, NR_WAVE), __shfl(acc.w, src, NR_WAVE));
       }
-    }
-    if (g == 0) {
-      if (slot == 0) {                                             // masked_row_out on the prefetched operands
-        float4 y = carry;
-        if (ep.addend) {
-          const float4 pre_add = ep.addend[o];
-          y = make_float4(__fadd_rn(y.x, pre_add.x), __fadd_rn(y.y, pre_add.y), __fadd_rn(y.z, pre_add.z),
-                          __fadd_rn(y.w, pre_add.w));
-        }
-        if (ep.Y) ep.Y[o] = y;
-        if (ep.sum_out) {
-          float4 si = pre_si;
-          if (ep.chain.a)
-            si = make_float4(__fadd_rn(si.x, pre_a.x), __fadd_rn(si.y, pre_a.y), __fadd_rn(si.z, pre_a.z),
-                             __fadd_rn(si.w, pre_a.w));
-          if (ep.chain.b)
-            si = make_float4(__fadd_rn(si.x, pre_b.x), __fadd_rn(si.y, pre_b.y), __fadd_rn(si.z, pre_b.z),
-                             __fadd_rn(si.w, pre_b.w));
-          ep.sum_out[o] = make_float4(__fadd_rn(si.x, y.x), __fadd_rn(si.y, y.y), __fadd_rn(si.z, y.z),
-                                      __fadd_rn(si.w, y.w));
-        }
-      } else if (slot < 0) {                                       // a segment of a one-chunk row: LDS
-        s_part[(size_t)(-slot - 1) * RS + c] = carry;
-      } else {                                                     // a segment of a multi-chunk row: global,
-        float* mine = ww_part + (size_t)(slot - 1) * 64 + c * 4;   // agent scope (written through)
-        __hip_atomic_store(mine + 0, carry.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(mine + 1, carry.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(mine + 2, carry.z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(mine + 3, carry.w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
+    });
+    if (g == 0)
+      ww_sublist_out(carry, slot, o, c, pre, ep, s_part + (size_t)(slot < 0 ? -slot - 1 : 0) * RS, ww_part);
     k = kn;
     e = en;
     col = coln;
@@ -922,34 +990,165 @@ __global__ __launch_bounds__(16 * NR_WAVE) void spmm_wanted_wave_kernel(
       const int hub = ww_gch[hi];
       const int4 hd = ww_hub[hub];                                 // {row, first partial slot, segments, chunks}
       if (!is_wanted(hd.x)) continue;
-      unsigned old = 0;
-      if (lane == 0) old = __hip_atomic_fetch_add(&ww_cnt[hub], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      old = __builtin_amdgcn_readfirstlane(old);
-      if (old != (unsigned)hd.w - 1u) continue;                    // another chunk of the row is still out
-      // all segment sums of the row, 16 at a time in flight, added in segment order
-      float4 sum = zero;
-      for (int s0 = 0; s0 < hd.z; s0 += 16) {
-        float4 q[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-          const float* qp = ww_part + ((size_t)hd.y + min(s0 + j, hd.z - 1)) * 64 + c * 4;
-          q[j].x = __hip_atomic_load(qp + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          q[j].y = __hip_atomic_load(qp + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          q[j].z = __hip_atomic_load(qp + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          q[j].w = __hip_atomic_load(qp + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-#pragma unroll
-        for (int j = 0; j < 16; ++j)
-          if (s0 + j < hd.z)
-            sum = make_float4(__fadd_rn(sum.x, q[j].x), __fadd_rn(sum.y, q[j].y), __fadd_rn(sum.z, q[j].z),
-                              __fadd_rn(sum.w, q[j].w));
-      }
-      if (g == 0)
-        masked_row_out(sum, (int64_t)hd.x * RS + c, ep.addend, true, ep.Y, ep.sum_in, ep.sum_out, &ep.chain);
-      if (lane == 0) __hip_atomic_store(&ww_cnt[hub], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-armed
+      ww_chunk_done(hub, hd, ww_cnt, ww_part, ep, lane, c, g);
     }
   }
   NR_WW_STAMP_END(4);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Row-masked hop, planned form.  The by-batch kernel above finds its work inside the step's latency chain:
+// every workgroup builds the batch's bit set, scans its ~306 static descriptors for the wanted ones, and runs
+// whatever the static deal left it (21 wanted sub-lists on average, 39-44 at most: 2-3 rounds of its 16 waves).
+// But a batch is known an epoch ahead (the sampler writes the whole stream and sorts every batch's occurrence
+// keys): spmm_wanted_epoch_plan_kernel turns the keys of ALL batches into item lists in one launch (a workgroup
+// per batch; layout and order: spmm_wanted_plan.h), and spmm_wanted_planned_kernel runs one batch's list — wave
+// w of workgroup g takes item 16 g + w, nothing is searched, and no workgroup holds more than one round.
+constexpr int kWpThreads = 1024;
+
+__global__ __launch_bounds__(kWpThreads) void spmm_wanted_epoch_plan_kernel(
+    const uint64_t* __restrict__ plans, int batch, int n_batches, int last_len, const int64_t* __restrict__ indptr,
+    const int4* __restrict__ ww_hub, int n_hubs, int n2, int stride, int4* __restrict__ sched) {
+  extern __shared__ uint32_t s_wp[];
+  uint32_t* s_key = s_wp;                     // [n2] sort keys of the distinct rows (~0: none)
+  int* s_off = (int*)(s_wp + n2);             // [n2] first item of sorted row j
+  __shared__ int s_scan[kWpThreads];
+  __shared__ int s_nhub, s_nrows;
+  const int tid = threadIdx.x, b = blockIdx.x;
+  const int n = 3 * (b == n_batches - 1 ? last_len : batch);
+  const uint64_t* keys = plans + 3 * (size_t)b * batch;
+  int4* items = sched + (size_t)b * stride;
+  if (tid == 0) { s_nhub = 0; s_nrows = 0; }
+  // the sorted keys hold every row once per occurrence: the first of a run stands for the row
+  for (int i = tid; i < n2; i += kWpThreads) {
+    uint32_t k = ~0u;
+    if (i < n) {
+      const int32_t row = (int32_t)(keys[i] >> 32);
+      const int32_t prev = i > 0 ? (int32_t)(keys[i - 1] >> 32) : -1;
+      if (row != prev) k = nr_wplan::sort_key(indptr[row + 1] - indptr[row], row);
+    }
+    s_key[i] = k;
+  }
+  __syncthreads();
+  for (int k = 2; k <= n2; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int i = tid; i < n2; i += kWpThreads) {
+        const int p = i ^ j;
+        if (p > i) {
+          const uint32_t x = s_key[i], y = s_key[p];
+          if ((x > y) == ((i & k) == 0)) { s_key[i] = y; s_key[p] = x; }
+        }
+      }
+      __syncthreads();
+    }
+  // slots of every sorted row, prefix-summed: thread t owns sorted positions [t * per, (t + 1) * per)
+  const int per = n2 / kWpThreads;
+  int sum = 0, hubs = 0, rows = 0;
+  for (int j = tid * per; j < (tid + 1) * per; ++j) {
+    const uint32_t k = s_key[j];
+    s_off[j] = sum;
+    if (k != ~0u) {
+      const int32_t row = nr_wplan::key_row(k);
+      const int64_t len = indptr[row + 1] - indptr[row];
+      sum += nr_wplan::slots_of(len);
+      hubs += nr_wplan::is_hub(len) ? 1 : 0;
+      ++rows;
+    }
+  }
+  s_scan[tid] = sum;
+  if (hubs) atomicAdd(&s_nhub, hubs);
+  if (rows) atomicAdd(&s_nrows, rows);
+  __syncthreads();
+  for (int off = 1; off < kWpThreads; off <<= 1) {
+    const int v = tid >= off ? s_scan[tid - off] : 0;
+    __syncthreads();
+    s_scan[tid] += v;
+    __syncthreads();
+  }
+  const int before = s_scan[tid] - sum, total = s_scan[kWpThreads - 1];
+  for (int j = tid * per; j < (tid + 1) * per; ++j) s_off[j] += before;
+  __syncthreads();
+  const int cap = stride - 1;                 // (the stride is an upper bound of `total`: never cut in practice)
+  const int n_hub_rows = s_nhub;
+  // hubs are the head of the order: the whole workgroup writes each one's items
+  for (int j = 0; j < n_hub_rows; ++j) {
+    const int32_t row = nr_wplan::key_row(s_key[j]);
+    const int64_t first = indptr[row], len = indptr[row + 1] - first;
+    int lo = 0, hi = n_hubs - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (ww_hub[mid].x < row) lo = mid + 1; else hi = mid;
+    }
+    const int part0 = ww_hub[lo].y, sl = nr_wplan::slots_of(len), o = s_off[j];
+    for (int s = tid; s < sl; s += kWpThreads)
+      if (o + s < cap) {
+        const nr_plan::Int4 it = nr_wplan::item_of(row, first, len, s, lo, part0);
+        items[1 + o + s] = make_int4(it.x, it.y, it.z, it.w);
+      }
+  }
+  for (int j = n_hub_rows + tid; j < n2; j += kWpThreads) {
+    const uint32_t k = s_key[j];
+    if (k == ~0u) continue;
+    const int32_t row = nr_wplan::key_row(k);
+    const int64_t first = indptr[row], len = indptr[row + 1] - first;
+    const int sl = nr_wplan::slots_of(len), o = s_off[j];
+    for (int s = 0; s < sl; ++s)
+      if (o + s < cap) {
+        const nr_plan::Int4 it = nr_wplan::item_of(row, first, len, s, 0, 0);
+        items[1 + o + s] = make_int4(it.x, it.y, it.z, it.w);
+      }
+  }
+  for (int i = 1 + min(total, cap) + tid; i < stride; i += kWpThreads) items[i] = make_int4(0, 0, 0, -1);
+  if (tid == 0) items[0] = make_int4(min(total, cap), s_nrows, 0, 0);
+}
+
+__global__ __launch_bounds__(16 * NR_WAVE) void spmm_wanted_planned_kernel(
+    const int4* __restrict__ items, const int4* __restrict__ ww_hub, float* ww_part, unsigned* ww_cnt,
+    const int32_t* __restrict__ indices, const float* __restrict__ vals, const float4* __restrict__ X, WantedEpi ep,
+    BatchLists bl) {
+  constexpr int RS = 16;
+  __shared__ float4 s_part[16 * RS];                               // a wave's segment sum (rows of 65..512 non-zeros)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int c = lane & 15, g = lane >> 4;
+  const int wg = blockIdx.x;
+  const int n_items = items[0].x;
+  ww_publish_batch(bl, wg, (int)gridDim.x, tid);
+  if (wg * 16 >= n_items) return;                                  // the grid is the stride bound: surplus workgroups
+  const int idx = wg * 16 + wave;
+  const int4 it = idx < n_items ? items[1 + idx] : make_int4(0, 0, 0, -1);
+  const int slot = it.x, len = it.y & 255, hub = (it.y >> 8) - 1, row = it.w;
+  const int64_t o = (int64_t)row * RS + c;
+  // segment 0 of a 65..512 row adds the row's segment sums after the barrier: it asks for the row's operands too
+  const bool head = slot < 0 && ((-slot - 1) & 15) == 0;
+  int4 hd = zero_int4();
+  WwPre pre;
+  if (row >= 0) {
+    int col = 0;
+    float val = 0.f;
+    if (lane < len) {
+      col = indices[(uint32_t)it.z + lane];
+      val = vals[(uint32_t)it.z + lane];
+    }
+    if (hub >= 0) hd = ww_hub[hub];                                // {row, first partial slot, segments, chunks}
+    const float4 carry = ww_sublist_sum(col, val, len, X, c, g,
+                                        [&]() { pre = ww_prefetch(ep, (slot == 0 || head) ? o : (int64_t)c); });
+    if (g == 0) ww_sublist_out(carry, slot, o, c, pre, ep, s_part + wave * RS, ww_part);
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_s_waitcnt(0);                                   // segment sums have left before a count moves
+  __syncthreads();
+  if (row < 0) return;
+  if (head && g == 0) {
+    const int ns = (-slot - 1) >> 4;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int sgm = 0; sgm < ns; ++sgm) {
+      const float4 q = s_part[(wave + sgm) * RS + c];
+      acc.x = __fadd_rn(acc.x, q.x); acc.y = __fadd_rn(acc.y, q.y);
+      acc.z = __fadd_rn(acc.z, q.z); acc.w = __fadd_rn(acc.w, q.w);
+    }
+    ww_sublist_out(acc, 0, o, c, pre, ep, nullptr, nullptr);       // masked_row_out on the prefetched operands
+  }
+  if (hub >= 0) ww_chunk_done(hub, hd, ww_cnt, ww_part, ep, lane, c, g);
 }
 
 size_t wanted_lds_bytes(const BlockedPlan* p) {
@@ -1083,6 +1282,10 @@ int nrhip_spmm_blocked_plan_create(const int64_t* h_indptr, const int32_t* h_ind
   p->nnz_cap = h.nnz_cap; p->ent_cap = h.ent_cap; p->colmask_ok = h.colmask_ok;
   p->wanted_ok = h.wanted_ok; p->w_ent_cap = h.w_ent_cap; p->w_nnz_cap = h.w_nnz_cap; p->w_bitmap_words = h.w_bitmap_words;
   p->ww_ok = h.ww_ok; p->ww_ent_cap = h.ww_ent_cap; p->ww_lds_slots = h.ww_lds_slots;
+  env = getenv("NEUREC_SPMM_WANTED_PLANNED");
+  p->n_hubs = (int)h.ww_hub.size();
+  p->wp_ok = h.ww_ok && opt.seg == nr_wplan::kSeg && n_rows <= nr_wplan::kMaxRows && !(env && env[0] == '0');
+  if (p->wp_ok) p->wp_profile = nr_wplan::slot_profile(h_indptr, n_rows);
   std::vector<nr_plan::Section> sections = nr_plan::plan_sections(*p, h);
   const size_t used = nr_plan::carve_sections(&sections, d_plan_buf);
   if (used > plan_bytes) {
@@ -1286,6 +1489,77 @@ int nrhip_spmm_blocked_wanted_batch(const void* plan, const int32_t* d_indices, 
                      LayerChain{(const float4*)d_layer_a, (const float4*)d_layer_b},
                      BatchLists{d_users, d_pos, d_neg, batch, n_users, d_row_flag, d_rows_out},
                      p->w_bitmap_words);
+  NR_LAUNCH_CHECK();
+  return NR_OK;
+}
+
+/* The same hop from a per-batch item list made an epoch ahead (spmm_wanted_plan.h).
+ * _has_wanted_planned: 1 when this plan can (wave-cooperative schedule, 64-pair segments, <= 2^19 rows,
+ * NEUREC_SPMM_WANTED_PLANNED != 0).
+ * _epoch_plan_bytes: records per batch (*stride, 16 bytes each) and the bytes of n_batches of them, for batches
+ * of up to `batch` triplets (3 * batch <= 16384, else NR_ERR_UNSUPPORTED).
+ * _epoch_plan: d_plans = nrhip_bpr_plan's output for the epoch stream (3 * batch keys per batch, the last batch
+ * last_len triplets); writes every batch's list at d_sched + k * stride * 16.  One launch, no host read.
+ * _wanted_planned: nrhip_spmm_blocked_wanted_batch on d_batch_sched = the batch's own records. */
+int nrhip_spmm_blocked_has_wanted_planned(const void* plan) {
+  return plan && ((const BlockedPlan*)plan)->wp_ok ? 1 : 0;
+}
+
+int nrhip_spmm_blocked_wanted_epoch_plan_bytes(const void* plan, int batch, int64_t n_batches, size_t* bytes,
+                                               int* stride) {
+  NR_REQUIRE(plan && bytes && stride && batch >= 1 && n_batches >= 0, NR_ERR_ARG,
+             "spmm_blocked_wanted_epoch_plan_bytes: bad arguments");
+  const BlockedPlan* p = (const BlockedPlan*)plan;
+  NR_REQUIRE(p->wp_ok, NR_ERR_UNSUPPORTED, "spmm_blocked_wanted_epoch_plan_bytes: no planned form for this plan");
+  NR_REQUIRE(3 * (int64_t)batch <= nr_wplan::kMaxKeys, NR_ERR_UNSUPPORTED,
+             "spmm_blocked_wanted_epoch_plan_bytes: batch %d > %d", batch, nr_wplan::kMaxKeys / 3);
+  const int64_t st = nr_wplan::stride_of(p->wp_profile, batch);
+  NR_REQUIRE(st < ((int64_t)1 << 24), NR_ERR_UNSUPPORTED, "spmm_blocked_wanted_epoch_plan_bytes: %lld items per batch",
+             (long long)st);
+  *stride = (int)st;
+  *bytes = (size_t)st * 16 * (size_t)n_batches;
+  return NR_OK;
+}
+
+int nrhip_spmm_blocked_wanted_epoch_plan(const void* plan, const int64_t* d_indptr, const uint64_t* d_plans, int batch,
+                                         int64_t n_batches, int last_len, void* d_sched, size_t sched_bytes,
+                                         void* stream) {
+  NR_REQUIRE(plan && d_indptr && d_plans && d_sched && batch >= 1 && n_batches >= 1 && last_len >= 1 &&
+                 last_len <= batch && n_batches < ((int64_t)1 << 30),
+             NR_ERR_ARG, "spmm_blocked_wanted_epoch_plan: bad arguments");
+  const BlockedPlan* p = (const BlockedPlan*)plan;
+  size_t need = 0;
+  int stride = 0;
+  NR_TRY(nrhip_spmm_blocked_wanted_epoch_plan_bytes(plan, batch, n_batches, &need, &stride));
+  NR_REQUIRE(sched_bytes >= need, NR_ERR_WORKSPACE, "spmm_blocked_wanted_epoch_plan: buffer %zu < %zu bytes",
+             sched_bytes, need);
+  int n2 = kWpThreads;
+  while (n2 < 3 * batch) n2 <<= 1;
+  hipLaunchKernelGGL(spmm_wanted_epoch_plan_kernel, dim3((unsigned)n_batches), dim3(kWpThreads), (size_t)n2 * 8,
+                     (hipStream_t)stream, d_plans, batch, (int)n_batches, last_len, d_indptr, p->ww_hub, p->n_hubs, n2,
+                     stride, (int4*)d_sched);
+  NR_LAUNCH_CHECK();
+  return NR_OK;
+}
+
+int nrhip_spmm_blocked_wanted_planned(const void* plan, const int32_t* d_indices, const float* d_vals,
+                                      const float* d_X, const float* d_sum_in, const float* d_layer_a,
+                                      const float* d_layer_b, float* d_sum_out, const int32_t* d_users,
+                                      const int32_t* d_pos, const int32_t* d_neg, int batch, int n_users,
+                                      uint8_t* d_row_flag, int32_t* d_rows_out, const void* d_batch_sched, int stride,
+                                      void* stream) {
+  NR_REQUIRE(plan && d_indices && d_vals && d_X && d_sum_in && d_sum_out && d_users && d_pos && d_neg &&
+                 d_row_flag && d_batch_sched && batch >= 1 && n_users >= 0 && stride > 1 && (stride - 1) % 16 == 0,
+             NR_ERR_ARG, "spmm_blocked_wanted_planned: bad arguments");
+  NR_REQUIRE(d_layer_a || !d_layer_b, NR_ERR_ARG, "spmm_blocked_wanted_planned: layer_b without layer_a");
+  const BlockedPlan* p = (const BlockedPlan*)plan;
+  NR_REQUIRE(p->wp_ok, NR_ERR_UNSUPPORTED, "spmm_blocked_wanted_planned: no planned form for this plan");
+  hipLaunchKernelGGL(spmm_wanted_planned_kernel, dim3((unsigned)((stride - 1) / 16)), dim3(16 * NR_WAVE), 0,
+                     (hipStream_t)stream, (const int4*)d_batch_sched, p->ww_hub, p->ww_part, p->ww_cnt, d_indices,
+                     d_vals, (const float4*)d_X,
+                     WantedEpi{nullptr, nullptr, (const float4*)d_sum_in, (float4*)d_sum_out,
+                               LayerChain{(const float4*)d_layer_a, (const float4*)d_layer_b}},
+                     BatchLists{d_users, d_pos, d_neg, batch, n_users, d_row_flag, d_rows_out});
   NR_LAUNCH_CHECK();
   return NR_OK;
 }

@@ -59,6 +59,13 @@ extern "C" int nrhip_spmm_csr_wanted_batch(const void* plan, const int32_t* d_in
                                            const int32_t* d_users, const int32_t* d_pos,
                                            const int32_t* d_neg, int batch, int n_users,
                                            uint8_t* d_row_flag, int32_t* d_rows_out, void* stream);
+extern "C" int nrhip_spmm_plan_has_wanted_planned(const void* plan, int d);
+extern "C" int nrhip_spmm_csr_wanted_planned(const void* plan, const int32_t* d_indices, const float* d_vals,
+                                             const float* d_X, int d, const float* d_sum_in, const float* d_layer_a,
+                                             const float* d_layer_b, float* d_sum_out, const int32_t* d_users,
+                                             const int32_t* d_pos, const int32_t* d_neg, int batch, int n_users,
+                                             uint8_t* d_row_flag, int32_t* d_rows_out, const void* d_batch_sched,
+                                             int stride, void* stream);
 extern "C" int nrhip_spmm_csr_wanted_layers(const void* plan, const int32_t* d_indices,
                                             const float* d_vals, const float* d_X, int d,
                                             const float* d_sum_in, const float* d_layer_a,
@@ -98,12 +105,14 @@ struct AdamArgs { float alpha, beta1, beta2, eps; };
 // phase 0: the whole step.  Column-sharded tables cut it at the head's inner products (the one quantity that
 // needs all D columns): phase 1 = forward + this rank's partial products into d_partials; phase 2 = head with
 // the summed products d_given + backward.
+// d_hop_sched / hop_stride: this batch's item list of the planned batch-rows hop (nrhip_spmm_wanted_epoch_plan), or
+// NULL: the hop finds its rows from the batch itself.
 static int lightgcn_fwd_bwd(const nrhip_lightgcn_buffers& b, const int32_t* d_users,
                             const int32_t* d_pos, const int32_t* d_neg, int batch,
                             const uint64_t* d_plan, float* d_loss2, void* stream,
                             const float** g_out, const AdamArgs* adam = nullptr,
                             bool* rearmed = nullptr, int phase = 0, float* d_partials = nullptr,
-                            const float* d_given = nullptr) {
+                            const float* d_given = nullptr, const void* d_hop_sched = nullptr, int hop_stride = 0) {
   const int L = b.n_layers, d = b.d;
   const bool skip = d >= 64;                 // the work-skipping variants exist for d >= 64
   // 0: no wanted-rows schedule; 1: it takes row flags; 2: it takes the batch itself and publishes
@@ -136,7 +145,11 @@ static int lightgcn_fwd_bwd(const nrhip_lightgcn_buffers& b, const int32_t* d_us
     }
     if (chain) {
       if (L - 1 == 1) { layer[0] = layer[1]; layer[1] = nullptr; }
-      if (wanted_form == 2)
+      if (wanted_form == 2 && d_hop_sched)
+        NR_TRY(nrhip_spmm_csr_wanted_planned(b.plan, b.indices, b.vals, src, d, acc_in, layer[0], layer[1],
+                                             b.Esum_rows, d_users, d_pos, d_neg, batch, b.n_users, b.row_flag,
+                                             b.batch_rows, d_hop_sched, hop_stride, stream));
+      else if (wanted_form == 2)
         NR_TRY(nrhip_spmm_csr_wanted_batch(b.plan, b.indices, b.vals, src, d, acc_in, layer[0], layer[1],
                                            b.Esum_rows, d_users, d_pos, d_neg, batch, b.n_users,
                                            b.row_flag, b.batch_rows, stream));
@@ -233,6 +246,30 @@ int nrhip_lightgcn_step(void* ctx, const int32_t* d_users, const int32_t* d_pos,
   return NR_OK;
 }
 
+// The same step with the batch-rows hop run from the batch's own item list (d_hop_sched: the batch's records of
+// an nrhip_spmm_wanted_epoch_plan output, hop_stride records; needs nrhip_spmm_plan_has_wanted_planned).
+int nrhip_lightgcn_step_planned(void* ctx, const int32_t* d_users, const int32_t* d_pos, const int32_t* d_neg,
+                                int batch, const uint64_t* d_plan, const void* d_hop_sched, int hop_stride,
+                                float alpha, float beta1, float beta2, float eps, float* d_loss2, void* stream) {
+  NR_TRY(lightgcn_check(ctx, d_users, d_pos, d_neg, batch));
+  if (batch == 0) return NR_OK;
+  const nrhip_lightgcn_buffers& b = ((LightGCNCtx*)ctx)->b;
+  NR_REQUIRE(d_hop_sched && b.n_layers > 0 && nrhip_spmm_plan_has_wanted_planned(b.plan, b.d) &&
+                 nrhip_spmm_plan_has_wanted(b.plan, b.d) == 2,
+             NR_ERR_UNSUPPORTED, "lightgcn_step_planned: no planned batch-rows hop for this context");
+  const float* g = nullptr;
+  const AdamArgs adam{alpha, beta1, beta2, eps};
+  bool rearmed = false;
+  NR_TRY(lightgcn_fwd_bwd(b, d_users, d_pos, d_neg, batch, d_plan, d_loss2, stream, &g, &adam, &rearmed, 0, nullptr,
+                          nullptr, d_hop_sched, hop_stride));
+  if (g)   // not folded into the last hop
+    NR_TRY(nrhip_adam_dense_tf2(b.E0, b.m, b.v, g, b.Greg, (int64_t)b.n_nodes * b.d, alpha, beta1, beta2, eps,
+                                stream));
+  if (rearmed) return NR_OK;
+  NR_TRY(nrhip_rows_clear(b.batch_rows, 3 * batch, b.d, b.Gstar, b.Greg, b.H, nullptr, b.row_flag, stream));
+  return NR_OK;
+}
+
 // Column-sharded tables (every rank holds d of the D embedding columns and steps on the WHOLE global batch;
 // neurec_amd/colshard.py): the step cut at the head's inner products.  _fwd: forward hops + this rank's partial
 // products, d_partials[3*batch]; the caller all-gathers them and sums them in rank order (nrhip_partials_sum);
@@ -245,6 +282,21 @@ int nrhip_lightgcn_step_colshard_fwd(void* ctx, const int32_t* d_users, const in
   const float* g = nullptr;
   return lightgcn_fwd_bwd(((LightGCNCtx*)ctx)->b, d_users, d_pos, d_neg, batch, nullptr, nullptr, stream, &g,
                           nullptr, nullptr, 1, d_partials, nullptr);
+}
+
+int nrhip_lightgcn_step_colshard_fwd_planned(void* ctx, const int32_t* d_users, const int32_t* d_pos,
+                                             const int32_t* d_neg, int batch, const void* d_hop_sched, int hop_stride,
+                                             float* d_partials, void* stream) {
+  NR_TRY(lightgcn_check(ctx, d_users, d_pos, d_neg, batch));
+  NR_REQUIRE(d_partials, NR_ERR_ARG, "lightgcn_step_colshard_fwd_planned: null output");
+  if (batch == 0) return NR_OK;
+  const nrhip_lightgcn_buffers& b = ((LightGCNCtx*)ctx)->b;
+  NR_REQUIRE(d_hop_sched && b.n_layers > 0 && nrhip_spmm_plan_has_wanted_planned(b.plan, b.d) &&
+                 nrhip_spmm_plan_has_wanted(b.plan, b.d) == 2,
+             NR_ERR_UNSUPPORTED, "lightgcn_step_colshard_fwd_planned: no planned batch-rows hop for this context");
+  const float* g = nullptr;
+  return lightgcn_fwd_bwd(b, d_users, d_pos, d_neg, batch, nullptr, nullptr, stream, &g, nullptr, nullptr, 1,
+                          d_partials, nullptr, d_hop_sched, hop_stride);
 }
 
 int nrhip_lightgcn_step_colshard_bwd(void* ctx, const int32_t* d_users, const int32_t* d_pos, const int32_t* d_neg,

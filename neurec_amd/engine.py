@@ -1115,6 +1115,50 @@ def ngcf_workspace(n_rows, device):
     return torch.empty(nbytes.value, dtype=torch.uint8, device=device)
 
 
+class EpochHopSchedule:
+    """Per-batch work lists of the batch-rows forward hop for a whole epoch (csrc/spmm_wanted_plan.h), made in ONE
+    launch from the sampler's epoch plan stream when the first batch of an epoch is seen: on the caller's stream, no
+    host synchronisation, one buffer reused from epoch to epoch.  A batch is recognised by what trainer.BprEpochSampler
+    puts on the plan tensors it yields (`epoch_plans` = (the epoch's plan stream, batch size, epoch number),
+    `batch_index`); a bare tensor or None gets None back and the step runs the hop that finds its rows itself."""
+
+    def __init__(self, A, d):
+        self.A, self.d = A, int(d)
+        self.ok = bool(_lib.lib.nrhip_spmm_plan_has_wanted_planned(A.plan, self.d)) and \
+            _lib.lib.nrhip_spmm_plan_has_wanted(A.plan, self.d) == 2
+        self.key, self.buf, self.stride, self.batch, self.n_batches, self.last_len = None, None, 0, 0, 0, 0
+
+    def for_batch(self, plan, n_triplets):
+        """(device address of this batch's records, records per batch) or None"""
+        stream = getattr(plan, "epoch_plans", None) if plan is not None else None
+        if not self.ok or stream is None:
+            return None
+        plans, batch, epoch = stream
+        if 3 * batch > 16384:                   # the one-workgroup planner's limit (nrhip_spmm_wanted_epoch_plan)
+            return None
+        key = (plans.data_ptr(), plans.numel(), int(batch), int(epoch))
+        if key != self.key:
+            self._build(plans, int(batch))
+            self.key = key
+        k = int(plan.batch_index)
+        if not (0 <= k < self.n_batches) or n_triplets != (self.last_len if k == self.n_batches - 1 else self.batch):
+            raise ValueError("batch %d of %d triplets is not a batch of its epoch stream" % (k, n_triplets))
+        return self.buf.data_ptr() + k * self.stride * 16, self.stride
+
+    def _build(self, plans, batch):
+        n = plans.numel() // 3
+        n_batches = (n + batch - 1) // batch
+        nbytes, stride = C.c_size_t(0), C.c_int(0)
+        call("nrhip_spmm_wanted_epoch_plan_bytes", self.A.plan, self.d, batch, n_batches, C.byref(nbytes),
+             C.byref(stride))
+        if self.buf is None or self.buf.numel() < nbytes.value:
+            self.buf = torch.empty(nbytes.value, dtype=torch.uint8, device=plans.device)
+        self.stride, self.batch, self.n_batches = stride.value, batch, n_batches
+        self.last_len = n - (n_batches - 1) * batch
+        call("nrhip_spmm_wanted_epoch_plan", self.A.plan, self.d, _ptr(self.A.indptr), _ptr(plans, torch.int64), batch,
+             n_batches, self.last_len, _ptr(self.buf), self.buf.numel(), _stream())
+
+
 class NativeStep:
     """Context of the native step drivers (csrc/step.hip): a record of device pointers owned by
     the Python engine object, which must outlive it."""
@@ -1233,12 +1277,22 @@ class NativeStep:
             raise TypeError("batch plan must be the int64 device tensor of %d keys bpr_plan made" % n_occ)
         return C.c_void_p(plan.data_ptr())
 
-    def lightgcn_step(self, users, pos, neg, st, loss2=None, plan=None):
+    def lightgcn_step(self, users, pos, neg, st, loss2=None, plan=None, hop=None):
+        """hop: EpochHopSchedule.for_batch's (address of the batch's work list, stride) or None"""
+        if hop is not None:
+            call("nrhip_lightgcn_step_planned", self.handle, self._idx(users), self._idx(pos), self._idx(neg),
+                 users.numel(), self._plan(plan, 3 * users.numel()), C.c_void_p(hop[0]), hop[1], float(st.alpha()),
+                 float(st.beta1), float(st.beta2), float(st.eps), _ptr(loss2, allow_none=True), _stream())
+            return
         call("nrhip_lightgcn_step", self.handle, self._idx(users), self._idx(pos), self._idx(neg),
              users.numel(), self._plan(plan, 3 * users.numel()), float(st.alpha()), float(st.beta1),
              float(st.beta2), float(st.eps), _ptr(loss2, allow_none=True), _stream())
 
-    def lightgcn_step_colshard_fwd(self, users, pos, neg, partials):
+    def lightgcn_step_colshard_fwd(self, users, pos, neg, partials, hop=None):
+        if hop is not None:
+            call("nrhip_lightgcn_step_colshard_fwd_planned", self.handle, self._idx(users), self._idx(pos),
+                 self._idx(neg), users.numel(), C.c_void_p(hop[0]), hop[1], _ptr(partials, torch.float32), _stream())
+            return
         call("nrhip_lightgcn_step_colshard_fwd", self.handle, self._idx(users), self._idx(pos), self._idx(neg),
              users.numel(), _ptr(partials, torch.float32), _stream())
 

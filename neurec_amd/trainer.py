@@ -90,13 +90,19 @@ class BprEpochSampler:
         """Yield device-tensor batches (views, no copies) for one epoch."""
         users, pos, neg = self.sample_epoch()
         B = self.batch_size
+        # what an engine needs to plan per-batch work for the WHOLE epoch in one launch (it is only handed the
+        # batch's plan): the epoch's plan stream, its batch size and which epoch the buffer holds
+        epoch_plans = (self._plan[:3 * self.n_local], B, self.epoch) if self.plans else None
         for k in range(len(self)):
             b, e = k * B, min((k + 1) * B, self.n_local)
             nb = neg[b * self.neg_num:e * self.neg_num]
             e2 = min((k + 2) * B, self.n_local)
+            plan = None
+            if self.plans:
+                plan = self._plan[3 * b:3 * e]
+                plan.epoch_plans, plan.batch_index = epoch_plans, k
             yield TripletBatch(users[b:e], pos[b:e],
-                               nb if self.neg_num == 1 else nb.view(-1, self.neg_num),
-                               self._plan[3 * b:3 * e] if self.plans else None,
+                               nb if self.neg_num == 1 else nb.view(-1, self.neg_num), plan,
                                self._plan[3 * e:3 * e2] if (self.plans and e2 > e) else None)
 
 
@@ -366,6 +372,7 @@ class LightGCNEngine:
         self.row_flag = torch.zeros(self.N, dtype=torch.uint8, device=dev)
         self.Gsync = None                    # allocated on first multi-GPU step
         self._ctx = E.NativeStep.for_lightgcn(self)
+        self._hop = E.EpochHopSchedule(self.A, self.d) if self.n_layers > 0 else None
 
     # -- forward: Esum = sum_k A^k E0  (LightGCN.py:132-149) -------------------------
     def propagate(self):
@@ -396,7 +403,10 @@ class LightGCNEngine:
         all-reduce of dL/dE0 across ranks — the step is then cut at that one exchange point.
         plan: the batch's TripletBatch.plan (None: sorted inside the step, one more launch)."""
         if grad_sync is None:
-            self._ctx.lightgcn_step(users, pos, neg, self.adam, loss_out, plan)
+            # a plan that says where it lies in its epoch's stream (the sampler's do): the batch-rows hop runs from
+            # the epoch's per-batch work lists, made in one launch when the first batch of an epoch arrives
+            hop = self._hop.for_batch(plan, users.numel()) if self._hop is not None else None
+            self._ctx.lightgcn_step(users, pos, neg, self.adam, loss_out, plan, hop=hop)
         else:
             if self.Gsync is None:
                 self.Gsync = torch.zeros_like(self.E0)
