@@ -1116,6 +1116,50 @@ int nrhip_wrmf_solve(const int64_t* d_indptr, const int32_t* d_indices, int n_ro
                      const int32_t* d_chunk_row, int n_chunks, float* d_X, void* d_ws, size_t ws_bytes,
                      void* stream);
 
+/* ---- ItemKNN (item-based nearest neighbours) ------------------------------
+ * Replaces: Compute_Similarity_Python.compute_similarity (ItemKNN.py:395-547), Compute_Similarity_Euclidean.
+ * compute_similarity (ItemKNN.py:60-214) and the dense scores `train_matrix.dot(W_sparse).toarray()` (ItemKNN.py:573).
+ * The train matrix R (n_users x n_items) comes in CSR and CSC form (the same pattern; indptr int64, ids int32) with
+ * the value arrays the similarity works on (raw ratings; mean-centred for adjusted / pearson; 1 for jaccard / dice /
+ * tversky) and two per-item arrays:
+ *     kind 0  cosine family   d_na = d_nb = sqrt(sumOfSquared); asymmetric: d_na = s^(2 alpha), d_nb = s^(2 (1 - alpha))
+ *                             w = c / (na[i] nb[j] + shrink + 1e-6)                                (ItemKNN.py:478-484)
+ *     kind 1  tanimoto        d_na = sumOfSquared;  w = c / (na[i] + na[j] - c + shrink + 1e-6)    (ItemKNN.py:488-490)
+ *     kind 2  dice            d_na = sumOfSquared;  w = c / (na[i] + na[j] + shrink + 1e-6)        (ItemKNN.py:492-494)
+ *     kind 3  tversky         d_na = sumOfSquared;  w = c / (c + (na[i] - c) ta + (na[j] - c) tb + shrink + 1e-6)
+ *                                                                                                  (ItemKNN.py:496-500)
+ *     kind 4  euclidean       d_na = sumOfSquared, d_nb = its square root;
+ *                             w = 1 / (sqrt((na[i] + na[j] - 2 c) / (nb[i] nb[j])) + shrink + 1e-9) (ItemKNN.py:146-181)
+ * with c = sum_u r_ui r_uj for column i (the diagonal is 0, ItemKNN.py:474 / 181).  The I x I matrix is never formed:
+ * a column's accumulator lives in LDS when n_items <= NRHIP_ITEMKNN_LDS_ITEMS, in a row of the workspace slab
+ * [block_cols][n_items] otherwise; columns are processed block_cols at a time.
+ * Selection (ItemKNN.py:513-523): the min(neighbor, n_items) largest entries of the column, exact zeros dropped.
+ * TIE RULE: the larger value wins; among equal values the LOWER item index wins (the reference's order among equal
+ * values is whatever argpartition leaves).  A column's list is stored in that order.
+ * Euclidean: a pair of items one or both of which have no interactions scores 0 (the reference: 0 and NaN) and is
+ * never stored.
+ * Output: d_w_idx / d_w_val [n_items][neighbor] (column i's neighbours j and W[j][i]; unused slots -1 / 0), d_w_cnt
+ * [n_items]; and W^T in CSR form for the scoring: d_t_indptr [n_items + 1], d_t_cols / d_t_vals [n_items * neighbor]
+ * (row j = the columns i whose list holds j, ascending i; the first d_t_indptr[n_items] entries are used).
+ * neighbor = 1..NRHIP_ITEMKNN_MAX_NEIGHBOR and n_items * neighbor <= 2^29 (the transpose's key sort
+ * keeps its padded count and strides in an int; above: NRHIP_ERR_UNSUPPORTED).  Every float sum is taken in a fixed
+ * order: two builds are bit-identical, and so are two score calls. */
+#define NRHIP_ITEMKNN_LDS_ITEMS 12288   /* the accumulator column stays in LDS up to this many items (48 KiB) */
+#define NRHIP_ITEMKNN_MAX_NEIGHBOR 1024 /* conf/ItemKNN.properties names 5..800 */
+int nrhip_itemknn_workspace_bytes(int n_items, int neighbor, int block_cols, size_t* bytes);
+int nrhip_itemknn_build(const int64_t* d_csc_indptr, const int32_t* d_csc_users, const float* d_csc_vals,
+                        const int64_t* d_csr_indptr, const int32_t* d_csr_items, const float* d_csr_vals,
+                        const float* d_na, const float* d_nb, int n_users, int n_items, int kind, float shrink,
+                        float tversky_alpha, float tversky_beta, int neighbor, int block_cols, int32_t* d_w_idx,
+                        float* d_w_val, int32_t* d_w_cnt, int64_t* d_t_indptr, int32_t* d_t_cols, float* d_t_vals,
+                        void* d_ws, size_t ws_bytes, void* stream);
+/* d_S [batch][ld_s] (ld_s >= n_items, the leading dimension of the score slab), row b = sum_{j in N(u_b)} r_{u_b j}
+ * W[j][:] (ItemKNN.py:573 for the users d_users only): the row is zeroed, then the history items are taken in CSR order
+ * (d_csr_vals: the RAW ratings), each adding its row of W^T. */
+int nrhip_itemknn_score(const int32_t* d_users, int batch, const int64_t* d_csr_indptr, const int32_t* d_csr_items,
+                        const float* d_csr_vals, int n_users, int n_items, const int64_t* d_t_indptr,
+                        const int32_t* d_t_cols, const float* d_t_vals, float* d_S, int64_t ld_s, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -313,6 +313,9 @@ SIGNATURES = {
     "nrhip_wrmf_workspace_bytes": [i32, i32, psz],
     "nrhip_wrmf_gram": [p, i32, i32, p, p, sz, p],
     "nrhip_wrmf_solve": [p, p, i32, p, i32, p, i32, f32, f32, p, p, i32, p, p, sz, p],
+    "nrhip_itemknn_workspace_bytes": [i32, i32, i32, psz],
+    "nrhip_itemknn_build": [p, p, p, p, p, p, p, p, i32, i32, i32, f32, f32, f32, i32, i32, p, p, p, p, p, p, p, sz, p],
+    "nrhip_itemknn_score": [p, i32, p, p, p, i32, i32, p, p, p, p, i64, p],
 }
 
 for _name, _args in SIGNATURES.items():
