@@ -1160,6 +1160,72 @@ int nrhip_itemknn_score(const int32_t* d_users, int batch, const int64_t* d_csr_
                         const float* d_csr_vals, int n_users, int n_items, const int64_t* d_t_indptr,
                         const int32_t* d_t_cols, const float* d_t_vals, float* d_S, int64_t ld_s, void* stream);
 
+/* ---- FISM (factored item similarity) ---------------------------------------
+ * Replaces: FISM._create_inference / _create_loss / the optimizer's gradients (FISM.py:66-92) run by
+ * `sess.run((self.loss, self.optimizer), feed_dict)` on histories padded to [B, Lmax] (FISM.py:119-139), and the
+ * per-user `sess.run(self.output)` over num_items copies of the history in predict() (FISM.py:154-180).
+ * An instance is (user u, item i, excluded item e or none, count n); H = the user's train row without e:
+ *     p = sum_{h in H} c1[h]      out = n^-alpha (p . Q[i]) + bias[i]               (FISM.py:68-72)
+ * The batch (d_users, d_items, d_third: `batch` entries each) expands as util/data_generator.py:29-54 states it:
+ *     pointwise (d_third = float labels)  label 1: e = i, n = |R_u|;  label 0: e none, n = |R_u| + 1
+ *         loss = pointwise_loss(kind, label, out) + reg_p l2_loss(p) + reg_q l2_loss(Q[i])        (FISM.py:86-88)
+ *     pairwise  (d_third = int32 negatives j)  positive side (i, e = i, n = |R_u|), negative side (j, e none,
+ *         n = |R_u| + 1); users with |R_u| <= 1 take no part (data_generator.py:13)
+ *         loss = pairwise_loss(kind, out_pos - out_neg) + reg_p l2_loss(p_pos) + reg_q (l2_loss(Q[j]) + l2_loss(Q[i]))
+ *                                                                                                 (FISM.py:79-83)
+ * with l2_loss = sum(x^2) / 2 and the loss kinds of nrhip_pointwise_mf_grad / nrhip_pairwise_mf_grad.
+ * Output: d_loss2 = (loss term, regulariser term); d_G_c1 [n_items][d] — EVERY row written, TF's gradient of c1 is
+ * dense because c1 is read through tf.concat (FISM.py:61); d_G_Q [n_items][d] and d_G_bias [n_items] — the rows of the
+ * batch's items only (sparse application, as embedding_lookup gives it), the other rows are left alone; d_flag_Q /
+ * d_flag_bias (uint8 [n_items], may be NULL): set to 1 for those rows (nrhip_optimizer_rows_tf); d_flag_c1 (uint8
+ * [n_items], may be NULL): set to 1 for every c1 row some instance of the batch pooled — for a caller that applies
+ * c1 by rows instead.  A pair with a user or an item outside the tables takes no part, both sides.  batch <=
+ * NRHIP_FISM_MAX_BATCH.
+ * The train matrix comes twice: CSR (d_indptr int64 [n_users + 1], d_indices int32) and transposed (d_t_indptr
+ * [n_items + 1], d_t_users ascending per item).  d_slot: int64 [n_users], zero before the first step; `step` >= 1 and
+ * larger at every call on the same d_slot.  Work buffers for N = batch (pointwise) or 2 batch (pairwise) instances:
+ * d_keys uint64 [2 N], d_inst int32 [4 N], d_n float [N], d_p / d_g float [N][d], d_scal float [8 N].
+ * Any history length; d = 1..NRHIP_FISM_MAX_D (above: NRHIP_ERR_UNSUPPORTED).  Every sum is taken in a fixed order
+ * (the pooled sum in fp64 partials combined by a fixed tree), no floating-point atomics: two calls on the same
+ * inputs are bit-identical. */
+#define NRHIP_FISM_MAX_D 128
+#define NRHIP_FISM_MAX_BATCH (1 << 24) /* 8 N work-buffer offsets stay inside an int for N = 2 batch */
+typedef struct nrhip_fism_step_args {
+  const int64_t* d_indptr;
+  const int32_t* d_indices;
+  const int64_t* d_t_indptr;
+  const int32_t* d_t_users;
+  const float* d_c1;
+  const float* d_Q;
+  const float* d_bias;
+  float* d_G_c1;
+  float* d_G_Q;
+  float* d_G_bias;
+  uint8_t* d_flag_Q;
+  uint8_t* d_flag_bias;
+  uint8_t* d_flag_c1;
+  const int32_t* d_users;
+  const int32_t* d_items;
+  const void* d_third;
+  uint64_t* d_keys;
+  int32_t* d_inst;
+  float* d_n;
+  float* d_p;
+  float* d_g;
+  float* d_scal;
+  int64_t* d_slot;
+  float* d_loss2;
+  int n_users, n_items, d, batch, pairwise, loss_kind, step;
+  float alpha, reg_p, reg_q;
+} nrhip_fism_step_args;
+int nrhip_fism_step(const nrhip_fism_step_args* args, void* stream);
+/* The evaluation's user factors (FISM.py:154-180 scores every item against the user's WHOLE train row, n = |R_u|):
+ * d_out [batch][ld] (ld >= d + 1), row b = [n^-alpha p_u | 1] for u = d_users[b] (d_users NULL: u = b), so that its
+ * inner product with [Q[i] | bias[i]] is the reference's `output`.  A user without train items (or outside the
+ * matrix) gets [0 | 1]: the bias alone (the reference raises KeyError there). */
+int nrhip_fism_user_factors(const int64_t* d_indptr, const int32_t* d_indices, int n_users, const float* d_c1, int d,
+                            float alpha, const int32_t* d_users, int batch, float* d_out, int64_t ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -136,6 +136,15 @@ class EvalRedoArgs(C.Structure):
                 ("ws_bytes", C.c_size_t)]
 
 
+class FismStepArgs(C.Structure):
+    """nrhip_fism_step_args (include/neurec_hip.h)"""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "indptr", "indices", "t_indptr", "t_users", "c1", "Q", "bias", "G_c1", "G_Q", "G_bias", "flag_Q", "flag_bias",
+        "flag_c1", "users", "items", "third", "keys", "inst", "n", "p", "g", "scal", "slot", "loss2")] + \
+        [(n, C.c_int) for n in ("n_users", "n_items", "d", "batch", "pairwise", "loss_kind", "step")] + \
+        [(n, C.c_float) for n in ("alpha", "reg_p", "reg_q")]
+
+
 # name -> argtypes; every function returns int status except where noted.
 SIGNATURES = {
     "nrhip_device_info": [C.POINTER(i32), C.POINTER(i32), psz, C.c_char_p, i32],
@@ -316,6 +325,8 @@ SIGNATURES = {
     "nrhip_itemknn_workspace_bytes": [i32, i32, i32, psz],
     "nrhip_itemknn_build": [p, p, p, p, p, p, p, p, i32, i32, i32, f32, f32, f32, i32, i32, p, p, p, p, p, p, p, sz, p],
     "nrhip_itemknn_score": [p, i32, p, p, p, i32, i32, p, p, p, p, i64, p],
+    "nrhip_fism_step": [C.POINTER(FismStepArgs), p],
+    "nrhip_fism_user_factors": [p, p, i32, p, i32, f32, p, i32, p, i64, p],
 }
 
 for _name, _args in SIGNATURES.items():
