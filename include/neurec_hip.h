@@ -1226,6 +1226,110 @@ int nrhip_fism_step(const nrhip_fism_step_args* args, void* stream);
 int nrhip_fism_user_factors(const int64_t* d_indptr, const int32_t* d_indices, int n_users, const float* d_c1, int d,
                             float alpha, const int32_t* d_users, int batch, float* d_out, int64_t ld, void* stream);
 
+/* ---- NAIS (neural attentive item similarity) ---------------------------------
+ * Replaces: NAIS._create_inference / _attention_mlp / _create_loss / the optimizer's gradients (NAIS.py:96-176) run by
+ * `sess.run((self.loss, self.optimizer), feed_dict)` on histories padded to [B, Lmax] (NAIS.py:197-217), and the
+ * per-user `sess.run(self.output)` over num_items copies of the history in predict() (NAIS.py:232-258).
+ * Instances, batch fields, loss kinds, d_G_c1 / d_G_Q / d_G_bias, the flags, d_slot / step and the two forms of the
+ * train matrix are nrhip_fism_step's; the rows of the CSR form must be ASCENDING.  With q = Q[i], per history item h_j:
+ *     x_j = c1[h_j] (.) q (algorithm 0) or [c1[h_j], q] (algorithm 1)        z_j = x_j W + b      (NAIS.py:157)
+ *     a_j = act(z_j) (activation 0 relu, 1 sigmoid, 2 tanh, other: identity)  (NAIS.py:158-163)
+ *     e_j = exp(a_j . h)   S = sum e_j   A_j = e_j / S^beta   p = sum A_j c1[h_j]                 (NAIS.py:165-176)
+ *     out = n^alpha (p . q) + bias[i]  — the exponent is +alpha                                  (NAIS.py:110-111)
+ *     loss = the pointwise / pairwise loss + reg_p l2_loss(the gathered c1[h_j]) + reg_q l2_loss(Q[i]) (NAIS.py:121-128)
+ * reference_mask != 0: an instance whose history is shorter than the longest of its side of the batch carries the
+ * reference's padding term (sequence_mask(num_idx) covers one zero row): S += exp(h . act(b)) for algorithm 0,
+ * exp(h . act(q W[d:2d] + b)) for algorithm 1, with its gradients.  reference_mask == 0: the softmax over H alone.
+ * d_W [d][w] (algorithm 1: [2 d][w]), d_b [w], d_h [w]; d_G_W / d_G_b / d_G_h: their dense gradients.
+ * Work buffers for N = batch (pointwise) or 2 batch (pairwise) instances: d_keys uint64 [2 N], d_inst int32 [4 N],
+ * d_n float [N], d_p float [N][d], d_scal float [8 N], d_off int64 [N], d_dWp float [N][d w], d_dbp / d_dhp float
+ * [N][w], d_dqp float [N][d], and d_rows float [row_cap][d]: the c1 row gradient of every history position of the
+ * batch, row_cap >= the sum of the instances' train-row lengths.  d_need int64 [2]: the call stores that sum in
+ * d_need[0] and keeps d_need[1] = the largest sum of any call (zero it once); positions beyond row_cap are not
+ * written, so a caller that finds d_need[1] > row_cap has lost gradient rows and must treat it as an error.
+ * c1_sort != 0: G_c1 is not taken by the walk over the transposed matrix but from d_pkeys uint64 [row_cap], the
+ * (item | position) keys of the ragged buffer's rows, sorted, each item's run summed in position order (row_cap <
+ * 2^31).  Both ways are fixed-order; their orders differ, so their sums may differ in the last bits.
+ * d = 1..NRHIP_NAIS_MAX_D, w = 1..NRHIP_NAIS_MAX_W (above: NRHIP_ERR_UNSUPPORTED), beta >= 0.  Every sum is taken in a
+ * fixed order, no floating-point atomics: two calls on the same inputs are bit-identical. */
+#define NRHIP_NAIS_MAX_D 128
+#define NRHIP_NAIS_MAX_W 64
+#define NRHIP_NAIS_MAX_BATCH (1 << 24)
+typedef struct nrhip_nais_step_args {
+  const int64_t* d_indptr;
+  const int32_t* d_indices;
+  const int64_t* d_t_indptr;
+  const int32_t* d_t_users;
+  const float* d_c1;
+  const float* d_Q;
+  const float* d_bias;
+  const float* d_W;
+  const float* d_b;
+  const float* d_h;
+  float* d_G_c1;
+  float* d_G_Q;
+  float* d_G_bias;
+  float* d_G_W;
+  float* d_G_b;
+  float* d_G_h;
+  uint8_t* d_flag_Q;
+  uint8_t* d_flag_bias;
+  uint8_t* d_flag_c1;
+  const int32_t* d_users;
+  const int32_t* d_items;
+  const void* d_third;
+  uint64_t* d_keys;
+  int32_t* d_inst;
+  float* d_n;
+  float* d_p;
+  float* d_scal;
+  int64_t* d_slot;
+  int64_t* d_off;
+  int64_t* d_need;
+  uint64_t* d_pkeys;
+  float* d_rows;
+  float* d_dWp;
+  float* d_dbp;
+  float* d_dhp;
+  float* d_dqp;
+  float* d_loss2;
+  int64_t row_cap;
+  int n_users, n_items, d, w, batch, pairwise, loss_kind, step, algorithm, activation, reference_mask, c1_sort;
+  float alpha, beta, reg_p, reg_q;
+} nrhip_nais_step_args;
+int nrhip_nais_step(const nrhip_nais_step_args* args, void* stream);
+/* predict() (NAIS.py:232-258): d_out [batch][ld] (ld >= n_items), row b = the scores of every item for u = d_users[b]
+ * on the user's WHOLE train row, the exact mask, n = |R_u|; a user without train items (or outside the matrix) gets
+ * d_bias bit for bit (the reference raises KeyError).  e(i, h) does not depend on the user: per tile of `tile` target
+ * items (a multiple of 256) e(i, h) and e(i, h)(c1[h] . Q[i]) are formed once for the distinct history items of the
+ * block (at most h_cap: the caller's bound, min(n_items, the block's row lengths summed)) and summed per user in CSR
+ * order.  Workspace: d_map / d_hs int32 [n_items], d_cnt int32 [1], d_E / d_F float [h_cap][tile]; algorithm 1:
+ * d_cW / d_qW float [n_items][w] = c1 W[0:d] and Q W[d:2d] + b, made by the call when project != 0.
+ * mfma != 0: the pair terms on the fp32 matrix cores (algorithm 0, d <= 16, w <= 16 only; else NRHIP_ERR_UNSUPPORTED). */
+typedef struct nrhip_nais_scores_args {
+  const int64_t* d_indptr;
+  const int32_t* d_indices;
+  const float* d_c1;
+  const float* d_Q;
+  const float* d_bias;
+  const float* d_W;
+  const float* d_b;
+  const float* d_h;
+  const int32_t* d_users;
+  float* d_out;
+  int32_t* d_map;
+  int32_t* d_hs;
+  int32_t* d_cnt;
+  float* d_E;
+  float* d_F;
+  float* d_cW;
+  float* d_qW;
+  int64_t ld;
+  int n_users, n_items, d, w, algorithm, activation, batch, h_cap, tile, project, mfma;
+  float alpha, beta;
+} nrhip_nais_scores_args;
+int nrhip_nais_scores(const nrhip_nais_scores_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -145,6 +145,27 @@ class FismStepArgs(C.Structure):
         [(n, C.c_float) for n in ("alpha", "reg_p", "reg_q")]
 
 
+class NaisStepArgs(C.Structure):
+    """nrhip_nais_step_args (include/neurec_hip.h)"""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "indptr", "indices", "t_indptr", "t_users", "c1", "Q", "bias", "W", "b", "h", "G_c1", "G_Q", "G_bias", "G_W",
+        "G_b", "G_h", "flag_Q", "flag_bias", "flag_c1", "users", "items", "third", "keys", "inst", "n", "p", "scal",
+        "slot", "off", "need", "pkeys", "rows", "dWp", "dbp", "dhp", "dqp", "loss2")] + [("row_cap", C.c_int64)] + \
+        [(n, C.c_int) for n in ("n_users", "n_items", "d", "w", "batch", "pairwise", "loss_kind", "step", "algorithm",
+                                "activation", "reference_mask", "c1_sort")] + \
+        [(n, C.c_float) for n in ("alpha", "beta", "reg_p", "reg_q")]
+
+
+class NaisScoresArgs(C.Structure):
+    """nrhip_nais_scores_args (include/neurec_hip.h)"""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "indptr", "indices", "c1", "Q", "bias", "W", "b", "h", "users", "out", "map", "hs", "cnt", "E", "F", "cW",
+        "qW")] + [("ld", C.c_int64)] + \
+        [(n, C.c_int) for n in ("n_users", "n_items", "d", "w", "algorithm", "activation", "batch", "h_cap", "tile",
+                                "project", "mfma")] + \
+        [(n, C.c_float) for n in ("alpha", "beta")]
+
+
 # name -> argtypes; every function returns int status except where noted.
 SIGNATURES = {
     "nrhip_device_info": [C.POINTER(i32), C.POINTER(i32), psz, C.c_char_p, i32],
@@ -327,6 +348,8 @@ SIGNATURES = {
     "nrhip_itemknn_score": [p, i32, p, p, p, i32, i32, p, p, p, p, i64, p],
     "nrhip_fism_step": [C.POINTER(FismStepArgs), p],
     "nrhip_fism_user_factors": [p, p, i32, p, i32, f32, p, i32, p, i64, p],
+    "nrhip_nais_step": [C.POINTER(NaisStepArgs), p],
+    "nrhip_nais_scores": [C.POINTER(NaisScoresArgs), p],
 }
 
 for _name, _args in SIGNATURES.items():
