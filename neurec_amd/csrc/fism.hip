@@ -5,34 +5,27 @@
 //     p = sum_{h in H} c1[h]        out = n^-alpha (p . Q[i]) + bias[i]
 // and neither the padded id matrix nor the [B, Lmax, d] gather exist: a wave walks the CSR row.
 //
-//   fism_prepare_kernel   the batch -> instances (pointwise: 1 per slot; pairwise: positive side then negative side)
-//                         and the 2N sort keys (user | position) and (n_users + item | position)
+//   prepare_kernel        history_common.h: the batch -> instances and the 2N sort keys
 //   fism_forward_kernel   (a) one wave per instance: 64 / DP history rows at a time (DP = lanes per row), fp64
 //                         partial sums per lane, combined across the row groups by a fixed xor tree
-//   fism_loss_kernel      (b) one workgroup: dout per instance, the loss and regulariser sums in a fixed order
-//   fism_rows_kernel      (c) per run of the sorted keys: a user's run head publishes its slot; an item's run head
-//                         sums G_Q[i] and G_bias[i] in batch order; one more wave per instance forms
-//                         g = dout n^-alpha Q[i] + reg_p p
-//   fism_walk_kernel      (c) one wave per item h: the column of the TRANSPOSED train matrix (users ascending) against
-//                         the slot map; G_c1[h] = sum over the batch's users of that column, ascending, over their
-//                         instances in batch order, of g — except the instances that excluded h.  Every row of G_c1
-//                         is written (TF's gradient of c1 is dense: it is read through tf.concat).
+//   loss_kernel           (b) history_common.h: dout per instance, the loss and regulariser sums in a fixed order
+//   fism_rows_kernel      (c) per run of the sorted keys (item_run_head, history_common.h): a user's run head publishes
+//                         its slot; an item's run head sums G_Q[i] and G_bias[i] in batch order; one more wave per
+//                         instance forms g = dout n^-alpha Q[i] + reg_p p
+//   fism_walk_kernel      (c) one wave per item h (walk_column, history_common.h): the column of the TRANSPOSED train
+//                         matrix (users ascending) against the slot map; G_c1[h] = sum over the batch's users of that
+//                         column, ascending, over their instances in batch order, of g — except the instances that
+//                         excluded h.  Every row of G_c1 is written (TF's gradient of c1 is dense: it is read through
+//                         tf.concat).
 //   fism_factors_kernel   (d) [n^-alpha p_u | 1] per user: the evaluation's user factors against [Q | bias]
 //
 // Every float sum is taken in a fixed order and nothing is accumulated with atomics: two runs are bit-identical.
-#include "nr_common.h"
+#include "history_common.h"
 #include "neurec_hip.h"
 
 namespace {
 
-constexpr uint64_t kSentinel = 0x7fffffffffffffffull;     // an instance that takes no part sorts behind every key
-constexpr int kScal = 8;                                  // floats per instance in d_scal
-enum { S_OUT = 0, S_COEFF = 1, S_PSQ = 2, S_QSQ = 3, S_DOUT = 4 };
-enum { F_VALID = 1, F_REGP = 2 };
-
-__device__ __forceinline__ double shfl_xor_f64(double x, int m) {
-  return __longlong_as_double((long long)nr_shfl_xor_u64((uint64_t)__double_as_longlong(x), m));
-}
+using namespace nr::hist;
 
 __device__ __forceinline__ float fism_coeff(float n, float alpha) { return n > 0.f ? powf(n, -alpha) : 0.f; }
 
@@ -61,43 +54,6 @@ __device__ __forceinline__ void fism_pool(const int64_t* __restrict__ indptr, co
 #pragma unroll
     for (int j = 0; j < CPL; ++j) acc[j] += shfl_xor_f64(acc[j], m);
   }
-}
-
-__global__ __launch_bounds__(256) void fism_prepare_kernel(nrhip_fism_step_args a, int N) {
-  const int b = blockIdx.x * 256 + threadIdx.x;
-  if (b >= N) return;
-  const int side = b / a.batch, t = b - side * a.batch;
-  const int u = a.d_users[t];
-  int item, excl, flags;
-  float n = 0.f;
-  bool ok = u >= 0 && u < a.n_users;
-  const int s = ok ? (int)(a.d_indptr[u + 1] - a.d_indptr[u]) : 0;
-  if (!a.pairwise) {
-    item = a.d_items[t];
-    const bool pos = ((const float*)a.d_third)[t] > 0.5f;
-    excl = pos ? item : -1;
-    n = (float)(pos ? s : s + 1);
-    flags = F_REGP;
-  } else {
-    // a pair takes part as a whole or not at all: both items must be table rows
-    const int pos_item = a.d_items[t], neg_item = ((const int32_t*)a.d_third)[t];
-    ok = ok && s > 1 && pos_item >= 0 && pos_item < a.n_items && neg_item >= 0 && neg_item < a.n_items;
-    item = side == 0 ? pos_item : neg_item;
-    excl = side == 0 ? pos_item : -1;
-    n = (float)(side == 0 ? s : s + 1);
-    flags = side == 0 ? F_REGP : 0;
-  }
-  ok = ok && item >= 0 && item < a.n_items;
-  if (ok) flags |= F_VALID;
-  a.d_inst[4 * b + 0] = u;
-  a.d_inst[4 * b + 1] = item;
-  a.d_inst[4 * b + 2] = excl;
-  a.d_inst[4 * b + 3] = flags;
-  a.d_n[b] = n;
-  a.d_keys[b] = ok ? (((uint64_t)(uint32_t)u << 32) | (uint32_t)b) : kSentinel;
-  a.d_keys[N + b] = ok ? (((uint64_t)(uint32_t)(a.n_users + item) << 32) | (uint32_t)b) : kSentinel;
-  if (ok && a.d_flag_Q) a.d_flag_Q[item] = 1;
-  if (ok && a.d_flag_bias) a.d_flag_bias[item] = 1;
 }
 
 template <int DP, int CPL>
@@ -136,48 +92,8 @@ __global__ __launch_bounds__(256) void fism_forward_kernel(nrhip_fism_step_args 
     const float coeff = fism_coeff(a.d_n[b], a.alpha);
     sc[S_OUT] = coeff * dot + a.d_bias[item];
     sc[S_COEFF] = coeff;
-    sc[S_PSQ] = psq;
+    sc[S_RSQ] = psq;
     sc[S_QSQ] = qsq;
-  }
-}
-
-__global__ __launch_bounds__(256) void fism_loss_kernel(nrhip_fism_step_args a, int N) {
-  __shared__ double s_a[256], s_b[256];
-  const int B = a.batch;
-  // tf.losses.sigmoid_cross_entropy is a MEAN over the batch, every other loss of util/learner.py a sum
-  const float scale = (!a.pairwise && a.loss_kind == nr::NR_POINT_CROSS_ENTROPY) ? 1.0f / (float)B : 1.0f;
-  double la = 0.0, lb = 0.0;
-  for (int t = threadIdx.x; t < B; t += 256) {
-    float* sp = a.d_scal + (int64_t)t * kScal;
-    if (!(a.d_inst[4 * t + 3] & F_VALID)) continue;
-    if (!a.pairwise) {
-      const float z = ((const float*)a.d_third)[t], x = sp[S_OUT];
-      la += (double)(scale * nr::pointwise_loss(a.loss_kind, z, x));
-      sp[S_DOUT] = scale * nr::pointwise_dloss(a.loss_kind, z, x);
-      lb += (double)(a.reg_p * (0.5f * sp[S_PSQ])) + (double)(a.reg_q * (0.5f * sp[S_QSQ]));
-    } else {
-      float* sn = a.d_scal + (int64_t)(B + t) * kScal;
-      const float y = sp[S_OUT] - sn[S_OUT];
-      la += (double)nr::pairwise_loss(a.loss_kind, y);
-      const float dl = nr::pairwise_dloss(a.loss_kind, y);
-      sp[S_DOUT] = dl;
-      sn[S_DOUT] = -dl;
-      lb += (double)(a.reg_p * (0.5f * sp[S_PSQ])) + (double)(a.reg_q * (0.5f * sn[S_QSQ] + 0.5f * sp[S_QSQ]));
-    }
-  }
-  s_a[threadIdx.x] = la;
-  s_b[threadIdx.x] = lb;
-  __syncthreads();
-  for (int s = 128; s >= 1; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-      s_a[threadIdx.x] += s_a[threadIdx.x + s];
-      s_b[threadIdx.x] += s_b[threadIdx.x + s];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0 && a.d_loss2) {
-    a.d_loss2[0] = (float)s_a[0];
-    a.d_loss2[1] = (float)s_b[0];
   }
 }
 
@@ -205,15 +121,10 @@ __global__ __launch_bounds__(256) void fism_rows_kernel(nrhip_fism_step_args a, 
     }
     return;
   }
-  const uint64_t key = a.d_keys[w];
-  if (key == kSentinel) return;
-  const uint32_t row = (uint32_t)(key >> 32);
-  if (w > 0 && (uint32_t)(a.d_keys[w - 1] >> 32) == row) return;            // not the head of its run
-  if ((int)row < a.n_users) {
-    if (lane == 0) a.d_slot[row] = ((int64_t)a.step << 32) | (uint32_t)w;
-    return;
-  }
-  const int item = (int)row - a.n_users;
+  const int head = item_run_head(a, w, lane);
+  if (head < 0) return;
+  const uint32_t row = (uint32_t)head;
+  const int item = head - a.n_users;
   float acc[CPL], q[CPL], gb = 0.f;
 #pragma unroll
   for (int j = 0; j < CPL; ++j) {
@@ -246,40 +157,8 @@ template <int CPL>
 __global__ __launch_bounds__(256) void fism_walk_kernel(nrhip_fism_step_args a, int N) {
   const int h = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (h >= a.n_items) return;
-  const int d = a.d;
-  float acc[CPL];
-#pragma unroll
-  for (int j = 0; j < CPL; ++j) acc[j] = 0.f;
-  const int64_t tb = a.d_t_indptr[h], te = a.d_t_indptr[h + 1];
-  for (int64_t base = tb; base < te; base += NR_WAVE) {
-    const int64_t k = base + lane;
-    const int u = k < te ? a.d_t_users[k] : -1;
-    const int64_t sl = (u >= 0 && u < a.n_users) ? a.d_slot[u] : 0;
-    const bool hit = (int)(sl >> 32) == a.step;
-    uint64_t mask = __ballot(hit);
-    while (mask) {                                        // the batch's users of this column, ascending
-      const int j0 = __builtin_ctzll(mask);
-      mask &= mask - 1;
-      const int k0 = __shfl((int)(uint32_t)sl, j0, NR_WAVE);
-      const uint32_t uu = (uint32_t)__shfl(u, j0, NR_WAVE);
-      for (int kk = k0; kk < 2 * N; ++kk) {               // that user's instances, in batch order
-        const uint64_t key = a.d_keys[kk];
-        if ((uint32_t)(key >> 32) != uu) break;
-        const int b = (int)(uint32_t)key;
-        if (a.d_inst[4 * b + 2] == h) continue;           // this instance pooled without h
-#pragma unroll
-        for (int j = 0; j < CPL; ++j) {
-          const int col = lane + j * NR_WAVE;
-          if (col < d) acc[j] += a.d_g[(int64_t)b * d + col];
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < CPL; ++j) {
-    const int col = lane + j * NR_WAVE;
-    if (col < d) a.d_G_c1[(int64_t)h * d + col] = acc[j];
-  }
+  walk_column<CPL>(a, N, h, lane, [](int) { return (int64_t)0; },
+                   [&](int b, int64_t) { return a.d_g + (int64_t)b * a.d; });
 }
 
 template <int DP, int CPL>
@@ -340,24 +219,22 @@ int nrhip_fism_step(const nrhip_fism_step_args* args, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const int N = a.batch * (a.pairwise ? 2 : 1), d = a.d;
   if (N > 0) {
-    hipLaunchKernelGGL(fism_prepare_kernel, dim3((N + 255) / 256), dim3(256), 0, st, a, N);
+    hipLaunchKernelGGL(prepare_kernel<nrhip_fism_step_args>, dim3((N + 255) / 256), dim3(256), 0, st, a, N);
     NR_LAUNCH_CHECK();
     NR_TRY(nrhip_sort_u64(a.d_keys, 2 * N, stream));
     NR_FISM_BY_WIDTH(fism_forward_kernel, dim3((N + 3) / 4), st, a, N);
     NR_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(fism_loss_kernel, dim3(1), dim3(256), 0, st, a, N);
+  hipLaunchKernelGGL(loss_kernel<nrhip_fism_step_args>, dim3(1), dim3(256), 0, st, a, N);
   NR_LAUNCH_CHECK();
   if (N > 0) {
     const dim3 grid((3 * N + 3) / 4);
-    if (d <= 64) hipLaunchKernelGGL(fism_rows_kernel<1>, grid, dim3(256), 0, st, a, N);
-    else hipLaunchKernelGGL(fism_rows_kernel<2>, grid, dim3(256), 0, st, a, N);
+    NR_HIST_BY_CPL(fism_rows_kernel, d, grid, st, a, N);
     NR_LAUNCH_CHECK();
   }
   if (a.n_items > 0) {
     const dim3 grid((a.n_items + 3) / 4);
-    if (d <= 64) hipLaunchKernelGGL(fism_walk_kernel<1>, grid, dim3(256), 0, st, a, N);
-    else hipLaunchKernelGGL(fism_walk_kernel<2>, grid, dim3(256), 0, st, a, N);
+    NR_HIST_BY_CPL(fism_walk_kernel, d, grid, st, a, N);
     NR_LAUNCH_CHECK();
   }
   return NR_OK;

@@ -10,19 +10,20 @@
 // than the longest of its side of the batch): exp(h . act(b)) for algorithm 0, exp(h . act(q W[d:2d] + b)) for 1.
 // Neither the padded id matrix nor a [B, Lmax, d] block exist: a wave walks the CSR row.
 //
-//   nais_prepare_kernel    the batch -> instances and the 2N sort keys, as fism_prepare_kernel
+//   prepare_kernel         history_common.h (shared with fism.hip): the batch -> instances and the 2N sort keys
 //   nais_scan_kernel       one workgroup: the exclusive prefix of the instances' row lengths (the ragged buffer's
 //                          offsets) and the longest history of each side
 //   nais_forward_kernel    one wave per instance, 64 / WP history rows at a time (WP lanes = the columns of W): ONE pass
 //                          gives e_j, S and sum e_j c1[h_j] in fp64 partials, combined by a fixed xor tree
-//   nais_loss_kernel       one workgroup: dout per instance, loss and regulariser sums in a fixed order
+//   loss_kernel            history_common.h: one workgroup, dout per instance, loss and regulariser sums in a fixed order
 //   nais_backward_kernel   one wave per instance: the position's terms again, ds_j by the closed form of the softmax's
 //                          cross term, the c1 row gradient of every position into the ragged [positions, d] buffer, and
 //                          the instance's partials of dW (top d rows), db, dh, dQ[i]
-//   nais_rows_kernel       per run of the sorted keys: a user's run head publishes its slot; an item's run head sums
-//                          G_Q[i] and G_bias[i] in batch order
-//   nais_walk_kernel       one wave per item h: the column of the transposed train matrix against the slot map;
-//                          G_c1[h] = the ragged buffer's rows of h, users ascending, their instances in batch order
+//   nais_rows_kernel       per run of the sorted keys (item_run_head, history_common.h): a user's run head publishes its
+//                          slot; an item's run head sums G_Q[i] and G_bias[i] in batch order
+//   nais_walk_kernel       one wave per item h (walk_column, history_common.h): the column of the transposed train matrix
+//                          against the slot map; G_c1[h] = the ragged buffer's rows of h, users ascending, their
+//                          instances in batch order
 //   nais_reduce_kernel     dW, db, dh: the instances' partials in batch order (algorithm 1: rows d..2d of dW are
 //                          sum_b Q[i_b] (x) db_b)
 //   nais_mark / compact / pairs / gather   predict(): the block's distinct history items H*, then per tile of target
@@ -31,21 +32,18 @@
 //                          of users instead of nnz I d w
 //
 // Every float sum is taken in a fixed order and nothing is accumulated with atomics: two runs are bit-identical.
-#include "nr_common.h"
+#include "history_common.h"
 #include "neurec_hip.h"
 
 namespace {
 
-constexpr uint64_t kSentinel = 0x7fffffffffffffffull;
-constexpr int kScal = 8;
-enum { S_OUT = 0, S_COEFF = 1, S_CSQ = 2, S_QSQ = 3, S_DOUT = 4, S_SUM = 5, S_SB = 6, S_PDQ = 7 };
-enum { F_VALID = 1, F_REGP = 2, F_PAD = 4 };
+using namespace nr::hist;
+
+enum { S_SUM = 5, S_SB = 6, S_PDQ = 7 };                  // d_scal beyond the shared slots
+enum { F_PAD = 4 };
 constexpr int kMaxD = NRHIP_NAIS_MAX_D, kMaxW = NRHIP_NAIS_MAX_W;
 constexpr int kWS = kMaxW + 1;                            // odd row stride of W in LDS at the bounds
 
-__device__ __forceinline__ double shfl_xor_f64(double x, int m) {
-  return __longlong_as_double((long long)nr_shfl_xor_u64((uint64_t)__double_as_longlong(x), m));
-}
 __device__ __forceinline__ float nais_act(int act, float z) {
   if (act == 0) return fmaxf(z, 0.f);
   if (act == 1) return 1.0f / (1.0f + expf(-z));
@@ -63,42 +61,6 @@ __device__ __forceinline__ float nais_pow(float x, float e) { return e == 0.f ? 
 __device__ __forceinline__ void wave_sync_lds() {
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();
-}
-
-__global__ __launch_bounds__(256) void nais_prepare_kernel(nrhip_nais_step_args a, int N) {
-  const int b = blockIdx.x * 256 + threadIdx.x;
-  if (b >= N) return;
-  const int side = b / a.batch, t = b - side * a.batch;
-  const int u = a.d_users[t];
-  int item, excl, flags;
-  float n = 0.f;
-  bool ok = u >= 0 && u < a.n_users;
-  const int s = ok ? (int)(a.d_indptr[u + 1] - a.d_indptr[u]) : 0;
-  if (!a.pairwise) {
-    item = a.d_items[t];
-    const bool pos = ((const float*)a.d_third)[t] > 0.5f;
-    excl = pos ? item : -1;
-    n = (float)(pos ? s : s + 1);
-    flags = F_REGP;
-  } else {
-    const int pos_item = a.d_items[t], neg_item = ((const int32_t*)a.d_third)[t];
-    ok = ok && s > 1 && pos_item >= 0 && pos_item < a.n_items && neg_item >= 0 && neg_item < a.n_items;
-    item = side == 0 ? pos_item : neg_item;
-    excl = side == 0 ? pos_item : -1;
-    n = (float)(side == 0 ? s : s + 1);
-    flags = side == 0 ? F_REGP : 0;
-  }
-  ok = ok && item >= 0 && item < a.n_items;
-  if (ok) flags |= F_VALID;
-  a.d_inst[4 * b + 0] = u;
-  a.d_inst[4 * b + 1] = item;
-  a.d_inst[4 * b + 2] = excl;
-  a.d_inst[4 * b + 3] = flags;
-  a.d_n[b] = n;
-  a.d_keys[b] = ok ? (((uint64_t)(uint32_t)u << 32) | (uint32_t)b) : kSentinel;
-  a.d_keys[N + b] = ok ? (((uint64_t)(uint32_t)(a.n_users + item) << 32) | (uint32_t)b) : kSentinel;
-  if (ok && a.d_flag_Q) a.d_flag_Q[item] = 1;
-  if (ok && a.d_flag_bias) a.d_flag_bias[item] = 1;
 }
 
 // d_off[b] = rows of the ragged buffer in front of instance b (its CSR row length each, the excluded slot included);
@@ -272,51 +234,11 @@ __global__ __launch_bounds__(256) void nais_forward_kernel(nrhip_nais_step_args 
     const float coeff = nais_pow(a.d_n[b], a.alpha);
     sc[S_OUT] = coeff * dot + a.d_bias[item];
     sc[S_COEFF] = coeff;
-    sc[S_CSQ] = (float)csq;
+    sc[S_RSQ] = (float)csq;
     sc[S_QSQ] = qsq;
     sc[S_SUM] = Sf;
     sc[S_SB] = SB;
     sc[S_PDQ] = dot;
-  }
-}
-
-__global__ __launch_bounds__(256) void nais_loss_kernel(nrhip_nais_step_args a, int N) {
-  __shared__ double s_a[256], s_b[256];
-  const int B = a.batch;
-  // tf.losses.sigmoid_cross_entropy is a MEAN over the batch, every other loss of util/learner.py a sum
-  const float scale = (!a.pairwise && a.loss_kind == nr::NR_POINT_CROSS_ENTROPY) ? 1.0f / (float)B : 1.0f;
-  double la = 0.0, lb = 0.0;
-  for (int t = threadIdx.x; t < B; t += 256) {
-    float* sp = a.d_scal + (int64_t)t * kScal;
-    if (!(a.d_inst[4 * t + 3] & F_VALID)) continue;
-    if (!a.pairwise) {
-      const float z = ((const float*)a.d_third)[t], x = sp[S_OUT];
-      la += (double)(scale * nr::pointwise_loss(a.loss_kind, z, x));
-      sp[S_DOUT] = scale * nr::pointwise_dloss(a.loss_kind, z, x);
-      lb += (double)(a.reg_p * (0.5f * sp[S_CSQ])) + (double)(a.reg_q * (0.5f * sp[S_QSQ]));
-    } else {
-      float* sn = a.d_scal + (int64_t)(B + t) * kScal;
-      const float y = sp[S_OUT] - sn[S_OUT];
-      la += (double)nr::pairwise_loss(a.loss_kind, y);
-      const float dl = nr::pairwise_dloss(a.loss_kind, y);
-      sp[S_DOUT] = dl;
-      sn[S_DOUT] = -dl;
-      lb += (double)(a.reg_p * (0.5f * sp[S_CSQ])) + (double)(a.reg_q * (0.5f * sn[S_QSQ] + 0.5f * sp[S_QSQ]));
-    }
-  }
-  s_a[threadIdx.x] = la;
-  s_b[threadIdx.x] = lb;
-  __syncthreads();
-  for (int s = 128; s >= 1; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-      s_a[threadIdx.x] += s_a[threadIdx.x + s];
-      s_b[threadIdx.x] += s_b[threadIdx.x + s];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0 && a.d_loss2) {
-    a.d_loss2[0] = (float)s_a[0];
-    a.d_loss2[1] = (float)s_b[0];
   }
 }
 
@@ -487,15 +409,10 @@ __global__ __launch_bounds__(256) void nais_rows_kernel(nrhip_nais_step_args a, 
   const int w = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int d = a.d;
   if (w >= 2 * N) return;
-  const uint64_t key = a.d_keys[w];
-  if (key == kSentinel) return;
-  const uint32_t row = (uint32_t)(key >> 32);
-  if (w > 0 && (uint32_t)(a.d_keys[w - 1] >> 32) == row) return;            // not the head of its run
-  if ((int)row < a.n_users) {
-    if (lane == 0) a.d_slot[row] = ((int64_t)a.step << 32) | (uint32_t)w;
-    return;
-  }
-  const int item = (int)row - a.n_users;
+  const int head = item_run_head(a, w, lane);
+  if (head < 0) return;
+  const uint32_t row = (uint32_t)head;
+  const int item = head - a.n_users;
   float acc[CPL], gb = 0.f;
 #pragma unroll
   for (int j = 0; j < CPL; ++j) acc[j] = 0.f;
@@ -522,51 +439,22 @@ template <int CPL>
 __global__ __launch_bounds__(256) void nais_walk_kernel(nrhip_nais_step_args a, int N) {
   const int h = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (h >= a.n_items) return;
-  const int d = a.d;
-  float acc[CPL];
-#pragma unroll
-  for (int j = 0; j < CPL; ++j) acc[j] = 0.f;
-  const int64_t tb = a.d_t_indptr[h], te = a.d_t_indptr[h + 1];
-  for (int64_t base = tb; base < te; base += NR_WAVE) {
-    const int64_t k = base + lane;
-    const int u = k < te ? a.d_t_users[k] : -1;
-    const int64_t sl = (u >= 0 && u < a.n_users) ? a.d_slot[u] : 0;
-    const bool hit = (int)(sl >> 32) == a.step;
-    uint64_t mask = __ballot(hit);
-    while (mask) {                                        // the batch's users of this column, ascending
-      const int j0 = __builtin_ctzll(mask);
-      mask &= mask - 1;
-      const int k0 = __shfl((int)(uint32_t)sl, j0, NR_WAVE);
-      const int uu = __shfl(u, j0, NR_WAVE);
+  walk_column<CPL>(
+      a, N, h, lane,
       // where h stands in the user's (ascending) row: the ragged buffer keeps the row's order
-      int64_t lo = a.d_indptr[uu], hi = a.d_indptr[uu + 1];
-      const int64_t r0 = lo;
-      while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (a.d_indices[mid] < h) lo = mid + 1; else hi = mid;
-      }
-      if (lo >= a.d_indptr[uu + 1] || a.d_indices[lo] != h) continue;
-      const int64_t rpos = lo - r0;
-      for (int kk = k0; kk < 2 * N; ++kk) {               // that user's instances, in batch order
-        const uint64_t key = a.d_keys[kk];
-        if ((uint32_t)(key >> 32) != (uint32_t)uu) break;
-        const int b = (int)(uint32_t)key;
-        if (a.d_inst[4 * b + 2] == h) continue;           // this instance attended without h
-        const int64_t r = a.d_off[b] + rpos;
-        if (r >= a.row_cap) continue;
-#pragma unroll
-        for (int j = 0; j < CPL; ++j) {
-          const int col = lane + j * NR_WAVE;
-          if (col < d) acc[j] += a.d_rows[r * d + col];
+      [&](int uu) -> int64_t {
+        int64_t lo = a.d_indptr[uu], hi = a.d_indptr[uu + 1];
+        const int64_t r0 = lo;
+        while (lo < hi) {
+          const int64_t mid = (lo + hi) >> 1;
+          if (a.d_indices[mid] < h) lo = mid + 1; else hi = mid;
         }
-      }
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < CPL; ++j) {
-    const int col = lane + j * NR_WAVE;
-    if (col < d) a.d_G_c1[(int64_t)h * d + col] = acc[j];
-  }
+        return (lo >= a.d_indptr[uu + 1] || a.d_indices[lo] != h) ? -1 : lo - r0;
+      },
+      [&](int b, int64_t rpos) -> const float* {
+        const int64_t r = a.d_off[b] + rpos;
+        return r >= a.row_cap ? nullptr : a.d_rows + r * a.d;
+      });
 }
 
 __global__ __launch_bounds__(256) void nais_fill_keys_kernel(nrhip_nais_step_args a) {
@@ -929,7 +817,7 @@ int nrhip_nais_step(const nrhip_nais_step_args* args, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const int N = a.batch * (a.pairwise ? 2 : 1), d = a.d;
   if (N > 0) {
-    hipLaunchKernelGGL(nais_prepare_kernel, dim3((N + 255) / 256), dim3(256), 0, st, a, N);
+    hipLaunchKernelGGL(prepare_kernel<nrhip_nais_step_args>, dim3((N + 255) / 256), dim3(256), 0, st, a, N);
     NR_LAUNCH_CHECK();
     hipLaunchKernelGGL(nais_scan_kernel, dim3(1), dim3(256), 0, st, a, N);
     NR_LAUNCH_CHECK();
@@ -937,7 +825,7 @@ int nrhip_nais_step(const nrhip_nais_step_args* args, void* stream) {
     NR_NAIS_BY_SHAPE(nais_forward_kernel, dim3((N + 3) / 4), st, a, N);
     NR_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(nais_loss_kernel, dim3(1), dim3(256), 0, st, a, N);
+  hipLaunchKernelGGL(loss_kernel<nrhip_nais_step_args>, dim3(1), dim3(256), 0, st, a, N);
   NR_LAUNCH_CHECK();
   if (a.c1_sort && a.row_cap > 0) {
     hipLaunchKernelGGL(nais_fill_keys_kernel, dim3((unsigned)((a.row_cap + 255) / 256)), dim3(256), 0, st, a);
@@ -947,8 +835,7 @@ int nrhip_nais_step(const nrhip_nais_step_args* args, void* stream) {
     NR_NAIS_BY_SHAPE(nais_backward_kernel, dim3((N + 3) / 4), st, a, N);
     NR_LAUNCH_CHECK();
     const dim3 grid((2 * N + 3) / 4);
-    if (d <= 64) hipLaunchKernelGGL(nais_rows_kernel<1>, grid, dim3(256), 0, st, a, N);
-    else hipLaunchKernelGGL(nais_rows_kernel<2>, grid, dim3(256), 0, st, a, N);
+    NR_HIST_BY_CPL(nais_rows_kernel, d, grid, st, a, N);
     NR_LAUNCH_CHECK();
   }
   if (a.c1_sort) {
@@ -956,14 +843,12 @@ int nrhip_nais_step(const nrhip_nais_step_args* args, void* stream) {
     if (a.row_cap > 0) {
       NR_TRY(nrhip_sort_u64(a.d_pkeys, (int)a.row_cap, stream));
       const dim3 grid((unsigned)((a.row_cap + 3) / 4));
-      if (d <= 64) hipLaunchKernelGGL(nais_segsum_kernel<1>, grid, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL(nais_segsum_kernel<2>, grid, dim3(256), 0, st, a);
+      NR_HIST_BY_CPL(nais_segsum_kernel, d, grid, st, a);
       NR_LAUNCH_CHECK();
     }
   } else if (a.n_items > 0) {
     const dim3 grid((a.n_items + 3) / 4);
-    if (d <= 64) hipLaunchKernelGGL(nais_walk_kernel<1>, grid, dim3(256), 0, st, a, N);
-    else hipLaunchKernelGGL(nais_walk_kernel<2>, grid, dim3(256), 0, st, a, N);
+    NR_HIST_BY_CPL(nais_walk_kernel, d, grid, st, a, N);
     NR_LAUNCH_CHECK();
   }
   const int entries = (a.algorithm == 1 ? 2 * d : d) * a.w + 2 * a.w;

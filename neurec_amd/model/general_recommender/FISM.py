@@ -13,20 +13,10 @@ generator states (positive side: the history without the item, n = |R_u|; negati
 n = |R_u| + 1; users with one train item take no part).  A user without train items scores `bias` alone (the
 reference raises KeyError).  Candidate mode returns the candidates' entries of the full-mode rows.
 """
-from time import time
-
-import numpy as np
-
-from ...data import PairwiseSampler, PointwiseSampler
 from ...util import timer
 from ...util.tool import get_initializer
 from ..AbstractRecommender import AbstractRecommender
-from ._common import predict_scores
-
-PAIRWISE_STRUCTURE = "pairwise structure: positive side = history without the item (n = |R_u|), negative side = " \
-                     "whole history (n = |R_u| + 1), users with one train item skipped"
-POINTWISE_STRUCTURE = "pointwise structure: label 1 = history without the item (n = |R_u|), label 0 = whole history " \
-                      "(n = |R_u| + 1)"
+from ._common import predict_scores, train_history_model
 
 
 class FISM(AbstractRecommender):
@@ -71,35 +61,7 @@ class FISM(AbstractRecommender):
 
     # ---------- training process -------
     def train_model(self):
-        import torch
-        self.logger.info(self.evaluator.metrics_info())
-        pairwise = self.is_pairwise is True
-        self.logger.info(PAIRWISE_STRUCTURE if pairwise else POINTWISE_STRUCTURE)
-        dev = self.engine.c1.device
-        if pairwise:
-            data_iter = PairwiseSampler(self.dataset, neg_num=1, batch_size=self.batch_size, shuffle=True,
-                                        as_tensors=True)
-            deg = np.diff(self.engine.csr.h_indptr)
-            n_instances = int(deg[deg > 1].sum())          # data_generator.py:13: users with more than one item
-        else:
-            data_iter = PointwiseSampler(self.dataset, neg_num=self.num_negatives, batch_size=self.batch_size,
-                                         shuffle=True, as_tensors=True)
-            n_instances = self.engine.csr.nnz * (1 + self.num_negatives)
-        losses = torch.zeros((max(len(data_iter), 1), 2), device=dev)
-        for epoch in range(1, self.num_epochs + 1):
-            training_start_time = time()
-            n = 0
-            for bat_users, bat_items, bat_third in data_iter:
-                self.engine.step(bat_users, bat_items, bat_third, losses[n])
-                n += 1
-            per_step = losses[:n].cpu().numpy()           # one D2H copy per epoch
-            total_loss = 0.0
-            for a, b in per_step:                          # `total_loss += loss`, FISM.py:130,139
-                total_loss += np.float32(a) + np.float32(b)
-            self.logger.info("[iter %d : loss : %f, time: %f]" % (epoch, total_loss / max(n_instances, 1),
-                                                                 time() - training_start_time))
-            if epoch % self.verbose == 0:
-                self.logger.info("epoch %d:\t%s" % (epoch, self.evaluate()))
+        train_history_model(self)
 
     @timer
     def evaluate(self):

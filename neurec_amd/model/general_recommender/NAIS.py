@@ -18,15 +18,12 @@ pairwise generator feeds empty histories); a user without train items scores `bi
 KeyError); the instances come from the device streams; multi-rank runs are refused; candidate mode returns the
 candidates' entries of the full-mode rows.
 """
-from time import time
-
 import numpy as np
 
-from ...data import PairwiseSampler, PointwiseSampler
 from ...util import timer
 from ...util.tool import get_initializer
 from ..AbstractRecommender import AbstractRecommender
-from .FISM import PAIRWISE_STRUCTURE, POINTWISE_STRUCTURE
+from ._common import train_history_model
 
 
 class NAIS(AbstractRecommender):
@@ -99,39 +96,9 @@ class NAIS(AbstractRecommender):
 
     # ---------- training process -------
     def train_model(self):
-        import torch
-        self.logger.info(self.evaluator.metrics_info())
-        pairwise = self.is_pairwise is True
-        self.logger.info(PAIRWISE_STRUCTURE if pairwise else POINTWISE_STRUCTURE)
-        dev = self.engine.c1.device
-        if pairwise:
-            data_iter = PairwiseSampler(self.dataset, neg_num=1, batch_size=self.batch_size, shuffle=True,
-                                        as_tensors=True)
-            deg = self.engine.h_deg
-            n_instances = int(deg[deg > 1].sum())
-        else:
-            data_iter = PointwiseSampler(self.dataset, neg_num=self.num_negatives, batch_size=self.batch_size,
-                                         shuffle=True, as_tensors=True)
-            n_instances = self.engine.csr.nnz * (1 + self.num_negatives)
-        losses = torch.zeros((max(len(data_iter), 1), 2), device=dev)
-        for epoch in range(1, self.num_epochs + 1):
-            training_start_time = time()
-            n = 0
-            batches = list(data_iter)
-            # the epoch's largest batch in history positions: one scalar copy, and the gradient buffer is sized to it
-            most = self.engine.max_positions([b[0] for b in batches])
-            for bat_users, bat_items, bat_third in batches:
-                self.engine.step(bat_users, bat_items, bat_third, losses[n], positions=most)
-                n += 1
-            per_step = losses[:n].cpu().numpy()           # one D2H copy per epoch
-            self.engine.verify()
-            total_loss = 0.0
-            for a, b in per_step:                          # `total_loss += loss`, NAIS.py:208,217
-                total_loss += np.float32(a) + np.float32(b)
-            self.logger.info("[iter %d : loss : %f, time: %f]" % (epoch, total_loss / max(n_instances, 1),
-                                                                 time() - training_start_time))
-            if epoch % self.verbose == 0:
-                self.logger.info("epoch %d:\t%s" % (epoch, self.evaluate()))
+        # the epoch's largest batch in history positions: one scalar copy, and the gradient buffer is sized to it
+        train_history_model(self, before_batches=lambda batches: {
+            "positions": self.engine.max_positions([b[0] for b in batches])}, after_epoch=self.engine.verify)
 
     @timer
     def evaluate(self):

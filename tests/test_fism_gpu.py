@@ -254,6 +254,56 @@ def test_edges_against_the_float64_restatement(d, batches):
     assert np.abs(eng.score(users).cpu().numpy() - want).max() <= 1e-5 * np.abs(want).max()
 
 
+def _with_slots_that_take_no_part(R, rs, pairwise):
+    """(the batch as the engine gets it, the same batch without the slots that take no part): pointwise 33 slots, four
+    of them with a user or an item that is no table row; pairwise 17 triples with user 1 (one train item), a negative
+    and a positive that are no table rows — before, between and after the slots that count"""
+    U, I = R.shape
+    if not pairwise:
+        users, items, third = _pointwise_batch(R, 33, rs)
+        users[0], users[7], items[21], items[32] = -1, U, -1, I
+        out = [0, 7, 21, 32]
+    else:
+        users, _, _ = _pointwise_batch(R, 17, rs)
+        items = np.asarray([R.indices[R.indptr[u] + rs.randint(R.indptr[u + 1] - R.indptr[u])] for u in users], np.int32)
+        third = (I - 1 - rs.randint(5, size=17)).astype(np.int32)
+        assert users[0] == 1 and R.indptr[2] - R.indptr[1] == 1
+        third[8], items[16] = I, -1
+        out = [0, 8, 16]
+    keep = np.setdiff1d(np.arange(len(users)), out)
+    return (users, items, third), (users[keep], items[keep], third[keep])
+
+
+@pytest.mark.parametrize("pairwise", [False, True])
+def test_slots_that_take_no_part(pairwise):
+    """a user or an item that is no table row (pairwise also: a user with one train item) takes its slot, or its whole
+    pair, out of the step: two gd steps give the tables and the loss of the float64 restatement fed the same batches
+    without those slots, 1e-5 max|want| as the edge shapes.  Square loss (pairwise: bpr): a sum over the instances —
+    the pointwise cross-entropy is a mean over the batch's length, slots that take no part included"""
+    import torch
+    from neurec_amd.fism import FISMEngine
+    R = _toy()
+    rs = np.random.RandomState(29)
+    d = 16
+    c1 = (0.1 * rs.randn(R.shape[1], d)).astype(np.float32)
+    Q = (0.1 * rs.randn(R.shape[1], d)).astype(np.float32)
+    b0 = (0.01 * rs.randn(R.shape[1])).astype(np.float32)
+    loss, lr = ("bpr", 0.2) if pairwise else ("square", 0.5)
+    eng = FISMEngine(c1, Q, R, lr, [0.01, 0.02], 0.5, 33, bias=b0, learner="gd", loss=loss, pairwise=pairwise)
+    st = F.State(c1, Q, b0, learner="gd", lr=lr)
+    loss2 = torch.zeros(2, device=eng.c1.device)
+    for k in range(2):
+        fed, kept = _with_slots_that_take_no_part(R, rs, pairwise)
+        got = _feed(eng, *fed, loss2)
+        want = F.step(st, R, *kept, pairwise, loss, 0.5, [0.01, 0.02])
+        print("step %d loss: device %.9g, restatement %.9g" % (k + 1, got, want))
+        assert abs(got - want) <= 1e-5 * abs(want), (k, got, want)
+        for name, t in zip(("c1", "Q", "bias"), _tables(eng)):
+            err = np.abs(t - st.var[name]).max()
+            print("step %d %s: err %.3g, bar %.3g" % (k + 1, name, err, 1e-5 * np.abs(st.var[name]).max()))
+            assert err <= 1e-5 * np.abs(st.var[name]).max(), (name, k, err)
+
+
 def test_embedding_size_129_is_refused():
     from neurec_amd.fism import FISMEngine
     R = _toy()

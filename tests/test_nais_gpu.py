@@ -12,7 +12,7 @@ from neurec_amd import defaults
 import fism_restatement as F
 import nais_restatement as NA
 from test_nais_cpu import CASES
-from test_fism_gpu import _pointwise_batch, _toy, _write_dataset
+from test_fism_gpu import _pointwise_batch, _toy, _with_slots_that_take_no_part, _write_dataset
 
 pytestmark = pytest.mark.gpu
 
@@ -111,15 +111,17 @@ def _tables_for(I, d, w, algorithm, rs):
             f(rs.randn(rows, w) / np.sqrt(rows)), f(sign * (0.3 + 0.2 * rs.rand(w))), f((1.0 + 0.3 * rs.randn(w)) / np.sqrt(w)))
 
 
-def _check_against_restatement(eng, T, R, batches, loss, pairwise, hy, mask, learner="gd", lr=0.2, c1_rows=False):
-    """device tables after every batch within 4x the restatement's own f32-to-f64 distance + 1e-5 max|want|"""
+def _check_against_restatement(eng, T, R, batches, loss, pairwise, hy, mask, learner="gd", lr=0.2, c1_rows=False,
+                               restated=None):
+    """device tables after every batch within 4x the restatement's own f32-to-f64 distance + 1e-5 max|want|;
+    restated: the batches the restatement gets where they are not the engine's"""
     import torch
     regs = [0.01, 0.02]
     s64 = NA.State(*T, learner=learner, lr=lr)
     s32 = NA.State(*T, learner=learner, lr=lr, dtype=np.float32)
     loss2 = torch.zeros(2, device=eng.c1.device)
-    for users, items, third in batches:
-        got = _feed(eng, users, items, third, loss2)
+    for fed, (users, items, third) in zip(batches, restated or batches):
+        got = _feed(eng, *fed, loss2)
         want = NA.step(s64, R, users, items, third, pairwise, loss, regs, mask=mask, c1_rows=c1_rows, **hy)
         w32 = NA.step(s32, R, users, items, third, pairwise, loss, regs, mask=mask, c1_rows=c1_rows, **hy)
         assert abs(got - want) <= 4 * abs(w32 - want) + 1e-5 * abs(want), (got, want, w32)
@@ -182,6 +184,26 @@ def test_c1_by_rows_option(learner):
     batches = [_pointwise_batch(R, 40, rs) for _ in range(2)]
     _check_against_restatement(eng, T, R, batches, "square", False, hy, "reference", learner=learner, lr=lr,
                                c1_rows=True)
+
+
+@pytest.mark.parametrize("pairwise", [False, True])
+def test_slots_that_take_no_part(pairwise):
+    """a user or an item that is no table row (pairwise also: a user with one train item) takes its slot, or its whole
+    pair, out of the step — the side's longest history, the padding term, included: two gd steps against the
+    restatement fed the same batches without those slots, under the edge shapes' bar.  Square loss (pairwise: bpr): a
+    sum over the instances — the pointwise cross-entropy is a mean over the batch's length, every slot included"""
+    from neurec_amd.nais import NAISEngine
+    R = _toy()
+    rs = np.random.RandomState(31)
+    T = _tables_for(R.shape[1], 16, 16, 0, rs)
+    hy = dict(algorithm=0, activation=2, alpha=0.5, beta=0.5)
+    loss = "bpr" if pairwise else "square"
+    eng = NAISEngine(T[0], T[1], T[3], T[4], R, 0.02, [0.01, 0.02], 0.5, 0.5, 33, algorithm=0, activation=2,
+                     loss=loss, pairwise=pairwise, learner="gd", bias=T[2], h=T[5], attention_mask="reference")
+    both = [_with_slots_that_take_no_part(R, rs, pairwise) for _ in range(2)]
+    _check_against_restatement(eng, T, R, [fed for fed, _ in both], loss, pairwise, hy, "reference", lr=0.02,
+                               restated=[kept for _, kept in both])
+    eng.verify()
 
 
 def test_gradient_buffer_follows_the_batch():
