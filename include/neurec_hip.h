@@ -1330,6 +1330,62 @@ typedef struct nrhip_nais_scores_args {
 } nrhip_nais_scores_args;
 int nrhip_nais_scores(const nrhip_nais_scores_args* args, void* stream);
 
+/* ---- FPMC (factorised personalised Markov chains) ------------------------------
+ * Replaces: FPMC._create_inference / _create_loss / the optimizer's gradients (model/sequential_recommender/
+ * FPMC.py:61-88) run by `sess.run((self.loss, self.optimizer), feed_dict)` (FPMC.py:111-128).
+ * An instance is (user u, recent item l, item i[, negative j]):
+ *     x(u, l, i) = <UI[u], IU[i]> + <IL[i], LI[l]>                                        (FPMC.py:64-69)
+ *     pointwise (d_third = float labels)   loss = pointwise_loss(kind, label, x(u,l,i))
+ *                                                 + reg l2_loss(UI[u], IU[i], IL[i], LI[l])              (FPMC.py:83-84)
+ *     pairwise  (d_third = int32 negatives) loss = pairwise_loss(kind, x(u,l,i) - x(u,l,j))
+ *                                                 + reg l2_loss(UI[u], IU[i], IL[i], LI[l], IU[j], IL[j]) (FPMC.py:77-80)
+ * with l2_loss = sum(x^2) / 2 and the loss kinds of nrhip_pointwise_mf_grad / nrhip_pairwise_mf_grad (the pointwise
+ * cross-entropy is the MEAN over `batch`).  UI[u] and LI[l] are regularised once per instance although the pairwise
+ * graph looks them up in both inferences.
+ * Output: d_loss2 = (loss term, regulariser term) of the tables as they come in; d_G_UI [n_users][d], d_G_IU / d_G_IL /
+ * d_G_LI [n_items][d]: the rows the batch looked up are STORED (the others are left alone: keep them zero), each the
+ * sum of its occurrences' gradients `g partner row + reg own row` in the order of nrhip_bpr_plan: by position in the
+ * batch, the first inference's lookups (positions 0..batch) before the second's (batch..2 batch; UI and LI: the
+ * gradient through the negative's score, without a regulariser term).  d_flag_* (uint8 per table row, may be NULL): set
+ * to 1 for those rows (nrhip_optimizer_rows_tf).
+ * A slot whose user is no row of UI or whose recent item, item or negative is outside [0, n_items) takes no part.
+ * Work buffers: d_keys uint64 [3 N] for N = batch (pointwise) or 2 batch (pairwise), d_scal float [4 batch].
+ * n_users + 2 n_items < 2^31; batch <= NRHIP_FPMC_MAX_BATCH; d = 1..NRHIP_FPMC_MAX_D (above: NRHIP_ERR_UNSUPPORTED).
+ * Every sum is taken in a fixed order, no floating-point atomics: two calls on the same inputs are bit-identical. */
+#define NRHIP_FPMC_MAX_D 128
+#define NRHIP_FPMC_MAX_BATCH (1 << 24)
+typedef struct nrhip_fpmc_step_args {
+  const float* d_UI;
+  const float* d_IU;
+  const float* d_IL;
+  const float* d_LI;
+  float* d_G_UI;
+  float* d_G_IU;
+  float* d_G_IL;
+  float* d_G_LI;
+  uint8_t* d_flag_UI;
+  uint8_t* d_flag_IU;
+  uint8_t* d_flag_IL;
+  uint8_t* d_flag_LI;
+  const int32_t* d_users;
+  const int32_t* d_recent;
+  const int32_t* d_items;
+  const void* d_third;
+  uint64_t* d_keys;
+  float* d_scal;
+  float* d_loss2;
+  int n_users, n_items, d, batch, pairwise, loss_kind;
+  float reg;
+} nrhip_fpmc_step_args;
+int nrhip_fpmc_step(const nrhip_fpmc_step_args* args, void* stream);
+/* The evaluation's user factors: d_out [batch][ld] (ld >= 2 d), row b = [UI[u] | LI[d_last[u]]] for u = d_users[b]
+ * (d_users NULL: u = b), so that its inner product with [IU[i] | IL[i]] is x(u, last(u), i) (FPMC.py:140-152).
+ * d_last int32 [n_users]: the user's most recent train item, -1 (or anything outside [0, n_items)): none — the second
+ * half is zeros and the score <UI[u], IU[i]> alone.  A user outside [0, n_users) gets a row of zeros. */
+int nrhip_fpmc_user_factors(const float* d_UI, const float* d_LI, int n_users, int n_items, int d,
+                            const int32_t* d_last, const int32_t* d_users, int batch, float* d_out, int64_t ld,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

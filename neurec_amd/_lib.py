@@ -166,6 +166,14 @@ class NaisScoresArgs(C.Structure):
         [(n, C.c_float) for n in ("alpha", "beta")]
 
 
+class FpmcStepArgs(C.Structure):
+    """nrhip_fpmc_step_args (include/neurec_hip.h)"""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "UI", "IU", "IL", "LI", "G_UI", "G_IU", "G_IL", "G_LI", "flag_UI", "flag_IU", "flag_IL", "flag_LI", "users",
+        "recent", "items", "third", "keys", "scal", "loss2")] + \
+        [(n, C.c_int) for n in ("n_users", "n_items", "d", "batch", "pairwise", "loss_kind")] + [("reg", C.c_float)]
+
+
 # name -> argtypes; every function returns int status except where noted.
 SIGNATURES = {
     "nrhip_device_info": [C.POINTER(i32), C.POINTER(i32), psz, C.c_char_p, i32],
@@ -350,6 +358,8 @@ SIGNATURES = {
     "nrhip_fism_user_factors": [p, p, i32, p, i32, f32, p, i32, p, i64, p],
     "nrhip_nais_step": [C.POINTER(NaisStepArgs), p],
     "nrhip_nais_scores": [C.POINTER(NaisScoresArgs), p],
+    "nrhip_fpmc_step": [C.POINTER(FpmcStepArgs), p],
+    "nrhip_fpmc_user_factors": [p, p, i32, i32, i32, p, p, i32, p, i64, p],
 }
 
 for _name, _args in SIGNATURES.items():

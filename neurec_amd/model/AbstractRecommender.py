@@ -51,3 +51,11 @@ class AbstractRecommender(object):
 
     def predict(self, user_ids, items):
         raise NotImplementedError
+
+
+class SeqAbstractRecommender(AbstractRecommender):
+    """base of `model/sequential_recommender/` (AbstractRecommender.py:48-52): the dataset must carry timestamps"""
+    def __init__(self, dataset, conf):
+        if dataset.time_matrix is None:
+            raise ValueError("Dataset does not contant time infomation!")
+        super(SeqAbstractRecommender, self).__init__(dataset, conf)
