@@ -1386,6 +1386,89 @@ int nrhip_fpmc_user_factors(const float* d_UI, const float* d_LI, int n_users, i
                             const int32_t* d_last, const int32_t* d_users, int batch, float* d_out, int64_t ld,
                             void* stream);
 
+/* ---- Fossil (FISM's long-term term + a personalised Markov term of order L) ------
+ * Replaces: Fossil._create_inference / _create_loss / the optimizer's gradients (model/sequential_recommender/
+ * Fossil.py:59-102) run by `sess.run((self.loss, self.optimizer), feed_dict)` on histories padded to [B, Lmax], and the
+ * per-user `sess.run(self.output)` of predict() (Fossil.py:177-217).  These symbols are additions: no existing struct
+ * changes and NRHIP_ABI_VERSION stays 4.
+ * An instance is (user u, item i, excluded item e or none, count n, recents r_0..r_{L-1}); H = the train row without e:
+ *     p = sum_{h in H} c1[h]     w_l = eta_bias[l] + eta[u][l]     s = sum_l w_l c1[r_l]
+ *     out = n^-alpha (p . Q[i]) + (s . Q[i]) + bias[i]                                    (Fossil.py:76-85)
+ * The batch (d_users, d_items, d_third: `batch` entries each; d_recents int32 [batch][L], MOST RECENT FIRST: column l
+ * meets eta column l) expands as the reference's generators state it:
+ *     pointwise (d_third = float labels)  label 1: e = i, n = |R_u| - 1;  label 0: e none, n = |R_u|
+ *         loss = pointwise_loss(kind, label, out) + reg_p l2_loss(p) + reg_q l2_loss(Q[i], c1[r_.])
+ *                + reg_eta l2_loss(eta[u], eta_bias)                                       (Fossil.py:99-102)
+ *     pairwise  (d_third = int32 negatives j)  positive side (i, e = i, n = |R_u| - 1), negative side (j, e none,
+ *         n = |R_u|), both on the slot's u and recents
+ *         loss = pairwise_loss(kind, out_pos - out_neg) + reg_p l2_loss(p_pos) + reg_q l2_loss(Q[j], Q[i], c1[r_.])
+ *                + reg_eta l2_loss(eta[u], eta_bias)                                       (Fossil.py:93-97)
+ * c1[r_.] and eta[u] enter the regulariser once per pointwise instance / per pair, eta_bias once per CALL (also when
+ * batch = 0).  A slot takes part only if its user and item(s) are table rows, |R_u| > L, and every one of its recents
+ * is a train item of its user — a recent outside the user's train row (or outside [0, n_items)) takes the whole slot
+ * out, both sides of a pair: the walk that sums G_c1 meets a recent through the train matrix, and no gradient is ever
+ * dropped silently.  A recent may equal the slot's own item; one item may stand at several columns.
+ * Tables: d_c1 / d_Q [n_items][d], d_bias [n_items], d_eta [n_users][L], d_eta_bias [L].  Output: d_loss2 = (loss term,
+ * regulariser term); d_G_c1 — EVERY row written (dense, c1 is read through tf.concat), by both routes: the pooled
+ * history and the recents; d_G_Q / d_G_bias — the rows of the batch's items, d_G_eta — the rows of the batch's users
+ * (the other rows are left alone); d_G_eta_bias [L] written whole.  d_flag_Q / d_flag_bias (uint8 [n_items]) and
+ * d_flag_eta (uint8 [n_users]), may be NULL: set to 1 for those rows; d_flag_c1 (may be NULL): every c1 row pooled or
+ * read as a recent.
+ * The train matrix, d_slot / step, and d_keys / d_inst / d_n / d_p / d_g / d_scal are nrhip_fism_step's; the rows of the
+ * CSR form must be ASCENDING and free of duplicates.  Further work buffers for N instances: d_x float [N][d]
+ * (n^-alpha p + s), d_dots float [N][L] (<c1[r_l], Q[i]>).  Neither a padded id matrix nor a [batch][L][d] block exists.
+ * d = 1..NRHIP_FOSSIL_MAX_D, L = 1..NRHIP_FOSSIL_MAX_ORDER (outside: NRHIP_ERR_UNSUPPORTED); batch <=
+ * NRHIP_FOSSIL_MAX_BATCH.  Every sum is taken in a fixed order, no floating-point atomics: two calls on the same
+ * inputs are bit-identical. */
+#define NRHIP_FOSSIL_MAX_D 128
+#define NRHIP_FOSSIL_MAX_ORDER 16 /* high_order; one lane per eta column, 16 columns per reduction row */
+#define NRHIP_FOSSIL_MAX_BATCH (1 << 24)
+typedef struct nrhip_fossil_step_args {
+  const int64_t* d_indptr;
+  const int32_t* d_indices;
+  const int64_t* d_t_indptr;
+  const int32_t* d_t_users;
+  const float* d_c1;
+  const float* d_Q;
+  const float* d_bias;
+  const float* d_eta;
+  const float* d_eta_bias;
+  float* d_G_c1;
+  float* d_G_Q;
+  float* d_G_bias;
+  float* d_G_eta;
+  float* d_G_eta_bias;
+  uint8_t* d_flag_Q;
+  uint8_t* d_flag_bias;
+  uint8_t* d_flag_c1;
+  uint8_t* d_flag_eta;
+  const int32_t* d_users;
+  const int32_t* d_recents;
+  const int32_t* d_items;
+  const void* d_third;
+  uint64_t* d_keys;
+  int32_t* d_inst;
+  float* d_n;
+  float* d_p;
+  float* d_x;
+  float* d_g;
+  float* d_dots;
+  float* d_scal;
+  int64_t* d_slot;
+  float* d_loss2;
+  int n_users, n_items, d, L, batch, pairwise, loss_kind, step;
+  float alpha, reg_p, reg_q, reg_eta;
+} nrhip_fossil_step_args;
+int nrhip_fossil_step(const nrhip_fossil_step_args* args, void* stream);
+/* The evaluation's user factors: d_out [batch][ld] (ld >= d + 1), row b =
+ * [ |R_u|^-alpha p_u + sum_l (eta_bias[l] + eta[u][l]) c1[d_last[u][l]] | 1 ] for u = d_users[b] (d_users NULL: u = b),
+ * so that its inner product with [Q[i] | bias[i]] is predict()'s `output`.  d_last int32 [n_users][L]: the item that
+ * meets eta column l, -1 (or anything outside [0, n_items)): the zero row.  A user outside the matrix gets [0 | 1]. */
+int nrhip_fossil_user_factors(const int64_t* d_indptr, const int32_t* d_indices, int n_users, int n_items,
+                              const float* d_c1, const float* d_eta, const float* d_eta_bias, const int32_t* d_last,
+                              int d, int L, float alpha, const int32_t* d_users, int batch, float* d_out, int64_t ld,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif

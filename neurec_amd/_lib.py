@@ -174,6 +174,16 @@ class FpmcStepArgs(C.Structure):
         [(n, C.c_int) for n in ("n_users", "n_items", "d", "batch", "pairwise", "loss_kind")] + [("reg", C.c_float)]
 
 
+class FossilStepArgs(C.Structure):
+    """nrhip_fossil_step_args (include/neurec_hip.h)"""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "indptr", "indices", "t_indptr", "t_users", "c1", "Q", "bias", "eta", "eta_bias", "G_c1", "G_Q", "G_bias",
+        "G_eta", "G_eta_bias", "flag_Q", "flag_bias", "flag_c1", "flag_eta", "users", "recents", "items", "third",
+        "keys", "inst", "n", "p", "x", "g", "dots", "scal", "slot", "loss2")] + \
+        [(n, C.c_int) for n in ("n_users", "n_items", "d", "L", "batch", "pairwise", "loss_kind", "step")] + \
+        [(n, C.c_float) for n in ("alpha", "reg_p", "reg_q", "reg_eta")]
+
+
 # name -> argtypes; every function returns int status except where noted.
 SIGNATURES = {
     "nrhip_device_info": [C.POINTER(i32), C.POINTER(i32), psz, C.c_char_p, i32],
@@ -360,6 +370,8 @@ SIGNATURES = {
     "nrhip_nais_scores": [C.POINTER(NaisScoresArgs), p],
     "nrhip_fpmc_step": [C.POINTER(FpmcStepArgs), p],
     "nrhip_fpmc_user_factors": [p, p, i32, i32, i32, p, p, i32, p, i64, p],
+    "nrhip_fossil_step": [C.POINTER(FossilStepArgs), p],
+    "nrhip_fossil_user_factors": [p, p, i32, i32, p, p, p, p, i32, i32, f32, p, i32, p, i64, p],
 }
 
 for _name, _args in SIGNATURES.items():

@@ -7,7 +7,8 @@
 //
 //   prepare_kernel        history_common.h: the batch -> instances and the 2N sort keys
 //   fism_forward_kernel   (a) one wave per instance: 64 / DP history rows at a time (DP = lanes per row), fp64
-//                         partial sums per lane, combined across the row groups by a fixed xor tree
+//                         partial sums per lane, combined across the row groups by a fixed xor tree (pool_row,
+//                         history_common.h)
 //   loss_kernel           (b) history_common.h: dout per instance, the loss and regulariser sums in a fixed order
 //   fism_rows_kernel      (c) per run of the sorted keys (item_run_head, history_common.h): a user's run head publishes
 //                         its slot; an item's run head sums G_Q[i] and G_bias[i] in batch order; one more wave per
@@ -27,35 +28,6 @@ namespace {
 
 using namespace nr::hist;
 
-__device__ __forceinline__ float fism_coeff(float n, float alpha) { return n > 0.f ? powf(n, -alpha) : 0.f; }
-
-// p of one CSR row without `excl`, columns c + j * DP of this lane, in every lane group
-template <int DP, int CPL>
-__device__ __forceinline__ void fism_pool(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
-                                          const float* __restrict__ c1, int d, int u, int excl, int lane,
-                                          double (&acc)[CPL], uint8_t* __restrict__ flag = nullptr) {
-  constexpr int G = NR_WAVE / DP;
-  const int grp = lane / DP, c = lane % DP;
-#pragma unroll
-  for (int j = 0; j < CPL; ++j) acc[j] = 0.0;
-  const int64_t b0 = indptr[u], e0 = indptr[u + 1];
-  for (int64_t k = b0 + grp; k < e0; k += G) {
-    const int h = indices[k];
-    if (h == excl) continue;
-    if (flag && c == 0) flag[h] = 1;                      // row application of c1: the rows this batch pooled
-#pragma unroll
-    for (int j = 0; j < CPL; ++j) {
-      const int col = c + j * DP;
-      if (col < d) acc[j] += (double)c1[(int64_t)h * d + col];
-    }
-  }
-#pragma unroll
-  for (int m = DP; m < NR_WAVE; m <<= 1) {
-#pragma unroll
-    for (int j = 0; j < CPL; ++j) acc[j] += shfl_xor_f64(acc[j], m);
-  }
-}
-
 template <int DP, int CPL>
 __global__ __launch_bounds__(256) void fism_forward_kernel(nrhip_fism_step_args a, int N) {
   const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -69,7 +41,7 @@ __global__ __launch_bounds__(256) void fism_forward_kernel(nrhip_fism_step_args 
   const int u = a.d_inst[4 * b], item = a.d_inst[4 * b + 1], excl = a.d_inst[4 * b + 2];
   const int d = a.d, grp = lane / DP, c = lane % DP;
   double acc[CPL];
-  fism_pool<DP, CPL>(a.d_indptr, a.d_indices, a.d_c1, d, u, excl, lane, acc, a.d_flag_c1);
+  pool_row<DP, CPL>(a.d_indptr, a.d_indices, a.d_c1, d, u, excl, lane, acc, a.d_flag_c1);
   float dot = 0.f, psq = 0.f, qsq = 0.f;
 #pragma unroll
   for (int j = 0; j < CPL; ++j) {
@@ -89,7 +61,7 @@ __global__ __launch_bounds__(256) void fism_forward_kernel(nrhip_fism_step_args 
     qsq += __shfl_xor(qsq, m, NR_WAVE);
   }
   if (lane == 0) {
-    const float coeff = fism_coeff(a.d_n[b], a.alpha);
+    const float coeff = count_coeff(a.d_n[b], a.alpha);
     sc[S_OUT] = coeff * dot + a.d_bias[item];
     sc[S_COEFF] = coeff;
     sc[S_RSQ] = psq;
@@ -178,8 +150,8 @@ __global__ __launch_bounds__(256) void fism_factors_kernel(const int64_t* __rest
     return;
   }
   double acc[CPL];
-  fism_pool<DP, CPL>(indptr, indices, c1, d, u, -1, lane, acc);
-  const float coeff = fism_coeff((float)(indptr[u + 1] - indptr[u]), alpha);
+  pool_row<DP, CPL>(indptr, indices, c1, d, u, -1, lane, acc);
+  const float coeff = count_coeff((float)(indptr[u + 1] - indptr[u]), alpha);
 #pragma unroll
   for (int j = 0; j < CPL; ++j) {
     const int col = c + j * DP;

@@ -1,17 +1,19 @@
-// history_common.h — what the steps of the history models share (fism.hip, nais.hip): an instance is
+// history_common.h — what the steps of the history models share (fism.hip, nais.hip, fossil.hip): an instance is
 // (user u, item i, excluded item e or none, count n) and the user is pooled from the train row without e.
 //
 //   prepare_kernel   the batch -> instances (pointwise: 1 per slot; pairwise: positive side then negative side) and
 //                    the 2N sort keys (user | position) and (n_users + item | position); an instance that takes no
 //                    part gets the sentinel key and no F_VALID
+//   pool_row         p of one CSR row without the excluded item, fp64 partials combined by a fixed xor tree
 //   loss_kernel      one workgroup: dout per instance, the loss and regulariser sums in a fixed order
-//   item_run_head    the rows kernels' opening: a user's run head publishes slot[user] = (step, position), an item's
-//                    run head gets its row n_users + item
-//   walk_column      one wave against a column of the TRANSPOSED train matrix (users ascending) and the slot map: the
-//                    batch's users of the column, ascending, their instances in batch order
+//   run_head / item_run_head   the rows kernels' opening: a user's run head publishes slot[user] = (step, position),
+//                    an item's run head gets its row n_users + item
+//   walk_column_acc / walk_column   one wave against a column of the TRANSPOSED train matrix (users ascending) and the
+//                    slot map: the batch's users of the column, ascending, their instances in batch order
 //
-// The kernels are templates over the argument struct: nrhip_fism_step_args and nrhip_nais_step_args name every field
-// read here alike.  Every float sum is taken in a fixed order.
+// The kernels are templates over the argument struct: nrhip_fism_step_args, nrhip_nais_step_args and
+// nrhip_fossil_step_args name every field read here alike.  A model whose instances differ from FISM's names a Rule
+// (PlainRule: FISM's and NAIS's).  Every float sum is taken in a fixed order.
 #pragma once
 #include "nr_common.h"
 
@@ -28,7 +30,20 @@ __device__ __forceinline__ double shfl_xor_f64(double x, int m) {
   return __longlong_as_double((long long)nr_shfl_xor_u64((uint64_t)__double_as_longlong(x), m));
 }
 
-template <class Args>
+// What a model may change of the instance rule and of the regulariser (the default: FISM, NAIS).
+//   kCount         n = |R_u| + kCount with the item excluded, |R_u| + 1 + kCount on the whole history
+//   takes_part     a further test of slot t (user u, a table row, with s train items)
+//   kExtraReg / extra_reg   a further regulariser term per pointwise instance / per pair, from its d_scal slots
+struct PlainRule {
+  static constexpr int kCount = 0;
+  static constexpr bool kExtraReg = false;
+  template <class Args>
+  __device__ static bool takes_part(const Args& a, int, int, int s) { return !a.pairwise || s > 1; }
+  template <class Args>
+  __device__ static double extra_reg(const Args&, const float*) { return 0.0; }
+};
+
+template <class Args, class Rule = PlainRule>
 __global__ __launch_bounds__(256) void prepare_kernel(Args a, int N) {
   const int b = blockIdx.x * 256 + threadIdx.x;
   if (b >= N) return;
@@ -38,19 +53,20 @@ __global__ __launch_bounds__(256) void prepare_kernel(Args a, int N) {
   float n = 0.f;
   bool ok = u >= 0 && u < a.n_users;
   const int s = ok ? (int)(a.d_indptr[u + 1] - a.d_indptr[u]) : 0;
+  ok = ok && Rule::takes_part(a, t, u, s);
   if (!a.pairwise) {
     item = a.d_items[t];
     const bool pos = ((const float*)a.d_third)[t] > 0.5f;
     excl = pos ? item : -1;
-    n = (float)(pos ? s : s + 1);
+    n = (float)((pos ? s : s + 1) + Rule::kCount);
     flags = F_REGP;
   } else {
     // a pair takes part as a whole or not at all: both items must be table rows
     const int pos_item = a.d_items[t], neg_item = ((const int32_t*)a.d_third)[t];
-    ok = ok && s > 1 && pos_item >= 0 && pos_item < a.n_items && neg_item >= 0 && neg_item < a.n_items;
+    ok = ok && pos_item >= 0 && pos_item < a.n_items && neg_item >= 0 && neg_item < a.n_items;
     item = side == 0 ? pos_item : neg_item;
     excl = side == 0 ? pos_item : -1;
-    n = (float)(side == 0 ? s : s + 1);
+    n = (float)((side == 0 ? s : s + 1) + Rule::kCount);
     flags = side == 0 ? F_REGP : 0;
   }
   ok = ok && item >= 0 && item < a.n_items;
@@ -66,7 +82,36 @@ __global__ __launch_bounds__(256) void prepare_kernel(Args a, int N) {
   if (ok && a.d_flag_bias) a.d_flag_bias[item] = 1;
 }
 
-template <class Args>
+__device__ __forceinline__ float count_coeff(float n, float alpha) { return n > 0.f ? powf(n, -alpha) : 0.f; }
+
+// p of one CSR row without `excl`, columns c + j * DP of this lane, in every lane group
+template <int DP, int CPL>
+__device__ __forceinline__ void pool_row(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
+                                         const float* __restrict__ c1, int d, int u, int excl, int lane,
+                                         double (&acc)[CPL], uint8_t* __restrict__ flag = nullptr) {
+  constexpr int G = NR_WAVE / DP;
+  const int grp = lane / DP, c = lane % DP;
+#pragma unroll
+  for (int j = 0; j < CPL; ++j) acc[j] = 0.0;
+  const int64_t b0 = indptr[u], e0 = indptr[u + 1];
+  for (int64_t k = b0 + grp; k < e0; k += G) {
+    const int h = indices[k];
+    if (h == excl) continue;
+    if (flag && c == 0) flag[h] = 1;                      // row application of c1: the rows this batch pooled
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) {
+      const int col = c + j * DP;
+      if (col < d) acc[j] += (double)c1[(int64_t)h * d + col];
+    }
+  }
+#pragma unroll
+  for (int m = DP; m < NR_WAVE; m <<= 1) {
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) acc[j] += shfl_xor_f64(acc[j], m);
+  }
+}
+
+template <class Args, class Rule = PlainRule>
 __global__ __launch_bounds__(256) void loss_kernel(Args a, int N) {
   __shared__ double s_a[256], s_b[256];
   const int B = a.batch;
@@ -81,6 +126,7 @@ __global__ __launch_bounds__(256) void loss_kernel(Args a, int N) {
       la += (double)(scale * nr::pointwise_loss(a.loss_kind, z, x));
       sp[S_DOUT] = scale * nr::pointwise_dloss(a.loss_kind, z, x);
       lb += (double)(a.reg_p * (0.5f * sp[S_RSQ])) + (double)(a.reg_q * (0.5f * sp[S_QSQ]));
+      if constexpr (Rule::kExtraReg) lb += Rule::extra_reg(a, sp);
     } else {
       float* sn = a.d_scal + (int64_t)(B + t) * kScal;
       const float y = sp[S_OUT] - sn[S_OUT];
@@ -89,6 +135,7 @@ __global__ __launch_bounds__(256) void loss_kernel(Args a, int N) {
       sp[S_DOUT] = dl;
       sn[S_DOUT] = -dl;
       lb += (double)(a.reg_p * (0.5f * sp[S_RSQ])) + (double)(a.reg_q * (0.5f * sn[S_QSQ] + 0.5f * sp[S_QSQ]));
+      if constexpr (Rule::kExtraReg) lb += Rule::extra_reg(a, sp);
     }
   }
   s_a[threadIdx.x] = la;
@@ -107,26 +154,30 @@ __global__ __launch_bounds__(256) void loss_kernel(Args a, int N) {
   }
 }
 
-// wave w of the sorted keys: -1 unless it stands on the head of an item's run, then the run's row n_users + item (the
-// upper half of its keys).  The head of a user's run publishes the user's slot on the way.
+// wave w of the sorted keys: -1 unless it stands on the head of a run, then the run's row (the upper half of its
+// keys: a user, or n_users + item).  The head of a user's run publishes the user's slot on the way.
 template <class Args>
-__device__ __forceinline__ int item_run_head(const Args& a, int w, int lane) {
+__device__ __forceinline__ int run_head(const Args& a, int w, int lane) {
   const uint64_t key = a.d_keys[w];
   if (key == kSentinel) return -1;
   const uint32_t row = (uint32_t)(key >> 32);
   if (w > 0 && (uint32_t)(a.d_keys[w - 1] >> 32) == row) return -1;         // not the head of its run
-  if ((int)row < a.n_users) {
-    if (lane == 0) a.d_slot[row] = ((int64_t)a.step << 32) | (uint32_t)w;
-    return -1;
-  }
+  if ((int)row < a.n_users && lane == 0) a.d_slot[row] = ((int64_t)a.step << 32) | (uint32_t)w;
   return (int)row;
 }
 
-// G_c1[h] = the sum of the rows of column h: per user of the batch in it, ascending, `at_user(user)` gives a token
-// (negative: the user adds nothing), and per instance b of that user, in batch order and unless b excluded h,
-// `row_of(b, token)` the row to add (nullptr: none)
-template <int CPL, class Args, class AtUser, class RowOf>
-__device__ __forceinline__ void walk_column(const Args& a, int N, int h, int lane, AtUser at_user, RowOf row_of) {
+// run_head for the heads of the items' runs alone
+template <class Args>
+__device__ __forceinline__ int item_run_head(const Args& a, int w, int lane) {
+  const int row = run_head(a, w, lane);
+  return row < a.n_users ? -1 : row;
+}
+
+// G_c1[h] = the sum over column h: per user of the batch in it, ascending, `at_user(user)` gives a token (negative:
+// the user adds nothing), and per instance b of that user, in batch order, `add(b, token, pooled, acc)` adds what the
+// instance gives to acc[j] (column lane + 64 j); pooled: b's history holds h (it did not exclude it)
+template <int CPL, class Args, class AtUser, class Add>
+__device__ __forceinline__ void walk_column_acc(const Args& a, int N, int h, int lane, AtUser at_user, Add add) {
   const int d = a.d;
   float acc[CPL];
 #pragma unroll
@@ -149,14 +200,7 @@ __device__ __forceinline__ void walk_column(const Args& a, int N, int h, int lan
         const uint64_t key = a.d_keys[kk];
         if ((uint32_t)(key >> 32) != (uint32_t)uu) break;
         const int b = (int)(uint32_t)key;
-        if (a.d_inst[4 * b + 2] == h) continue;           // this instance pooled without h
-        const float* row = row_of(b, token);
-        if (!row) continue;
-#pragma unroll
-        for (int j = 0; j < CPL; ++j) {
-          const int col = lane + j * NR_WAVE;
-          if (col < d) acc[j] += row[col];
-        }
+        add(b, token, a.d_inst[4 * b + 2] != h, acc);
       }
     }
   }
@@ -165,6 +209,22 @@ __device__ __forceinline__ void walk_column(const Args& a, int N, int h, int lan
     const int col = lane + j * NR_WAVE;
     if (col < d) a.d_G_c1[(int64_t)h * d + col] = acc[j];
   }
+}
+
+// walk_column_acc where an instance adds one row, and only when it pooled h: `row_of(b, token)` (nullptr: none)
+template <int CPL, class Args, class AtUser, class RowOf>
+__device__ __forceinline__ void walk_column(const Args& a, int N, int h, int lane, AtUser at_user, RowOf row_of) {
+  const int d = a.d;
+  walk_column_acc<CPL>(a, N, h, lane, at_user, [&](int b, int64_t token, bool pooled, float (&acc)[CPL]) {
+    if (!pooled) return;                                  // this instance pooled without h
+    const float* row = row_of(b, token);
+    if (!row) return;
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) {
+      const int col = lane + j * NR_WAVE;
+      if (col < d) acc[j] += row[col];
+    }
+  });
 }
 
 }  // namespace hist

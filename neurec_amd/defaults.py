@@ -34,6 +34,10 @@ MODELS = {
                  ("anneal_cap", "0.2"), ("total_anneal_steps", "2000"),
                  ("weight_init_method", "xavier_normal"), ("bias_init_method", "tnormal"),
                  ("stddev", "0.01"), ("verbose", "1")],
+    "Fossil": [("epochs", "100"), ("batch_size", "256"), ("embedding_size", "16"), ("regs", "[0.00,0.00,0.0]"),
+               ("alpha", "0.5"), ("learning_rate", "0.001"), ("learner", "adagrad"), ("is_pairwise", "True"),
+               ("high_order", "3"), ("num_neg", "4"), ("loss_function", "bpr"), ("init_method", "uniform"),
+               ("stddev", "0.01"), ("verbose", "1")],
 }
 
 

@@ -1,4 +1,5 @@
-"""What the engines of the history models share (neurec_amd/fism.py, neurec_amd/nais.py; csrc/history_common.h).
+"""What the engines of the history models share (neurec_amd/fism.py, neurec_amd/nais.py, neurec_amd/fossil.py;
+csrc/history_common.h).
 
 A user is not a table row but a pooling of the `c1` rows of the train history; an instance is (user, item, excluded
 item or none, count).  Both engines hold c1 / Q / bias, the train matrix and its transpose, one optimiser state per
@@ -118,9 +119,15 @@ class HistoryEngine:
     def _fill(self, a):
         """the fields of the argument struct beyond the shared ones"""
 
-    def step(self, users, items, third, loss_out):
-        """pointwise: third = labels (float32); pairwise: third = negative items (int32).  loss_out: 2 floats on the
-        device, (loss term, regulariser term) of the batch before the update."""
+    def _field(self, t, dtype):
+        """the device address of a batch field"""
+        return _ptr(t, dtype)
+
+    def _apply_more(self):
+        """the applications of a model's tables beyond c1 / Q / bias and its dense variables"""
+
+    def gradients(self, users, items, third, loss_out):
+        """the C call alone: loss_out and the gradient buffers self.G (and the row flags); no table moves"""
         B = int(users.numel())
         if B > self.max_batch:
             raise ValueError("batch larger than max_batch")
@@ -134,8 +141,8 @@ class HistoryEngine:
             setattr(a, k, _ptr(getattr(self, k)))
             setattr(a, "G_" + k, _ptr(self.G[k]))
         a.flag_Q, a.flag_bias, a.flag_c1 = _addr(self.flag_Q), _addr(self.flag_bias), _addr(self.flag_c1)
-        a.users, a.items = _ptr(users, torch.int32), _ptr(items, torch.int32)
-        a.third = _ptr(third, torch.int32 if self.pairwise else torch.float32)
+        a.users, a.items = self._field(users, torch.int32), self._field(items, torch.int32)
+        a.third = self._field(third, torch.int32 if self.pairwise else torch.float32)
         a.keys, a.inst, a.n, a.p, a.scal = (_ptr(t) for t in (self._keys, self._inst, self._n, self._p, self._scal))
         a.slot, a.loss2 = _ptr(self._slot), _ptr(loss_out, torch.float32)
         a.n_users, a.n_items, a.d, a.batch = self.n_users, self.n_items, self.d, B
@@ -143,6 +150,9 @@ class HistoryEngine:
         a.alpha, a.reg_p, a.reg_q = self.alpha, self.reg_p, self.reg_q
         self._fill(a)
         call(self.STEP, C.byref(a), _stream())
+
+    def apply(self):
+        """the applications of self.G, in the order TF-1.12 runs them here"""
         if self.c1_rows:
             self._apply_rows("c1", self.flag_c1)
             self._apply_dense(self._dense_names)
@@ -150,4 +160,11 @@ class HistoryEngine:
             self._apply_dense(("c1",) + self._dense_names)
         self._apply_rows("Q", self.flag_Q)
         self._apply_rows("bias", self.flag_bias)
+        self._apply_more()
         self.adam.advance()
+
+    def step(self, users, items, third, loss_out):
+        """pointwise: third = labels (float32); pairwise: third = negative items (int32).  loss_out: 2 floats on the
+        device, (loss term, regulariser term) of the batch before the update."""
+        self.gradients(users, items, third, loss_out)
+        self.apply()
