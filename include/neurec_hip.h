@@ -1469,6 +1469,63 @@ int nrhip_fossil_user_factors(const int64_t* d_indptr, const int32_t* d_indices,
                               int d, int L, float alpha, const int32_t* d_users, int batch, float* d_out, int64_t ld,
                               void* stream);
 
+/* ---- HRM (hierarchical representation model: max / avg pooling over the user and its recents) ------
+ * Replaces: HRM._create_inference / _create_loss / the optimizer's gradients (model/sequential_recommender/
+ * HRM.py:62-95) run by `sess.run((self.loss, self.optimizer), feed_dict)` (HRM.py:115-123).  These symbols are
+ * additions: no existing struct changes and NRHIP_ABI_VERSION stays 4.
+ * An instance is (user u, recents r_0..r_{L-1}, item i, label y) over d_P [n_users][d] and d_V [n_items][d]:
+ *     s = session_agg over l of V[r_l]  (L >= 2: session_max ? column-wise max : mean;  L == 1: V[r_0])  (HRM.py:68-77)
+ *     h = pre_agg over {P[u], s}        (pre_max ? column-wise max : the mean of the two)               (HRM.py:78-81)
+ *     x = <h, V[i]>                                                                                     (HRM.py:82-83)
+ *     loss = pointwise_loss(kind, y, x) + reg l2_loss(P[u], V[r_.], V[i])                               (HRM.py:90-91)
+ * with l2_loss = sum(x^2) / 2 per occurrence and the loss kinds of nrhip_pointwise_mf_grad (the cross-entropy is the
+ * MEAN over `batch`).  A max sends a column's derivative to the inputs equal to the maximum, in equal shares
+ * (indicators / num_selected * grad); an item that stands twice among one instance's recents ties with itself.
+ * Batch: d_users, d_items, d_labels (float): `batch` entries each; d_recents int32 [batch][L], in any order.
+ * Output: d_loss2 = (loss term, regulariser term) of the tables as they come in; d_G_P / d_G_V: the rows the batch
+ * looked up are STORED (the others are left alone: keep them zero), each the sum of its occurrences' gradients in the
+ * order of its sort keys: a V row's target occurrences by batch slot, then its recent occurrences by (slot, column); a
+ * P row's occurrences by batch slot.  d_flag_P / d_flag_V (uint8 per table row, may be NULL): set to 1 for those rows
+ * (nrhip_optimizer_rows_tf).
+ * A slot whose user is no row of P or whose item or any recent is outside [0, n_items) takes no part.
+ * Work buffers: d_keys uint64 [batch (2 + L)], d_scal float [4 batch], d_s and d_ds float [batch][d] (the session row
+ * and its already-divided derivative: the max's shares are decided once and read back by the row sums); no
+ * [batch][L][d] block exists.
+ * n_users + n_items < 2^31 - 1; batch <= NRHIP_HRM_MAX_BATCH; d = 1..NRHIP_HRM_MAX_D, L = 1..NRHIP_HRM_MAX_ORDER
+ * (outside: NRHIP_ERR_UNSUPPORTED).  Every sum is taken in a fixed order, no floating-point atomics: two calls on the
+ * same inputs are bit-identical. */
+#define NRHIP_HRM_MAX_D 128
+#define NRHIP_HRM_MAX_ORDER 16 /* high_order; one lane per recent in the narrowest lane group */
+#define NRHIP_HRM_MAX_BATCH (1 << 24)
+typedef struct nrhip_hrm_step_args {
+  const float* d_P;
+  const float* d_V;
+  float* d_G_P;
+  float* d_G_V;
+  uint8_t* d_flag_P;
+  uint8_t* d_flag_V;
+  const int32_t* d_users;
+  const int32_t* d_recents;
+  const int32_t* d_items;
+  const float* d_labels;
+  uint64_t* d_keys;
+  float* d_scal;
+  float* d_s;
+  float* d_ds;
+  float* d_loss2;
+  int n_users, n_items, d, L, batch, pre_max, session_max, loss_kind;
+  float reg;
+} nrhip_hrm_step_args;
+int nrhip_hrm_step(const nrhip_hrm_step_args* args, void* stream);
+/* The evaluation's user factors: d_out [batch][ld] (ld >= d), row b = h_u for u = d_users[b] (d_users NULL: u = b), so
+ * that its inner product with V[i] is predict()'s `output` (HRM.py:135-163).  d_last int32 [n_users][L]: the items the
+ * user is pooled over, -1 (or anything outside [0, n_items)): a slot that takes no part — the session row is the max /
+ * mean over the m slots that do, one item alone is that item, and with none h_u = P[u].  The pooling is the step's own
+ * code.  A user outside [0, n_users) gets a row of zeros. */
+int nrhip_hrm_user_factors(const float* d_P, const float* d_V, int n_users, int n_items, int d, int L, int pre_max,
+                           int session_max, const int32_t* d_last, const int32_t* d_users, int batch, float* d_out,
+                           int64_t ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

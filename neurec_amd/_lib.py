@@ -184,6 +184,15 @@ class FossilStepArgs(C.Structure):
         [(n, C.c_float) for n in ("alpha", "reg_p", "reg_q", "reg_eta")]
 
 
+class HrmStepArgs(C.Structure):
+    """nrhip_hrm_step_args (include/neurec_hip.h)"""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "P", "V", "G_P", "G_V", "flag_P", "flag_V", "users", "recents", "items", "labels", "keys", "scal", "s", "ds",
+        "loss2")] + \
+        [(n, C.c_int) for n in ("n_users", "n_items", "d", "L", "batch", "pre_max", "session_max", "loss_kind")] + \
+        [("reg", C.c_float)]
+
+
 # name -> argtypes; every function returns int status except where noted.
 SIGNATURES = {
     "nrhip_device_info": [C.POINTER(i32), C.POINTER(i32), psz, C.c_char_p, i32],
@@ -372,6 +381,8 @@ SIGNATURES = {
     "nrhip_fpmc_user_factors": [p, p, i32, i32, i32, p, p, i32, p, i64, p],
     "nrhip_fossil_step": [C.POINTER(FossilStepArgs), p],
     "nrhip_fossil_user_factors": [p, p, i32, i32, p, p, p, p, i32, i32, f32, p, i32, p, i64, p],
+    "nrhip_hrm_step": [C.POINTER(HrmStepArgs), p],
+    "nrhip_hrm_user_factors": [p, p, i32, i32, i32, i32, i32, i32, p, p, i32, p, i64, p],
 }
 
 for _name, _args in SIGNATURES.items():

@@ -38,6 +38,10 @@ MODELS = {
                ("alpha", "0.5"), ("learning_rate", "0.001"), ("learner", "adagrad"), ("is_pairwise", "True"),
                ("high_order", "3"), ("num_neg", "4"), ("loss_function", "bpr"), ("init_method", "uniform"),
                ("stddev", "0.01"), ("verbose", "1")],
+    "HRM": [("epochs", "3"), ("batch_size", "256"), ("embedding_size", "16"), ("reg_mf", "0"), ("topK", "10"),
+            ("learning_rate", "0.001"), ("learner", "adam"), ("pre_agg", "max"), ("session_agg", "max"),
+            ("high_order", "2"), ("num_neg", "4"), ("loss_function", "cross_entropy"), ("init_method", "normal"),
+            ("stddev", "0.01"), ("verbose", "1")],
 }
 
 
