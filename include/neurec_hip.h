@@ -391,7 +391,11 @@ int nrhip_adam_dense_tf_multi(int n_tensors, float* const* d_vars_host, float* c
                               float beta1, float beta2, float eps, void* stream);
 /* Row-sparse helpers over a list of row ids of a [*, d] buffer (repeats allowed):
  * dst[row] = src[row] / denom; and zeroing of the listed rows of up to four buffers plus a
- * per-row byte flag (any of them may be NULL). */
+ * per-row byte flag (any of them may be NULL).
+ * Empty work is no error: with n_listed == 0 (these two, nrhip_rows_gather*, nrhip_rows_scatter_add,
+ * nrhip_mark_rows), n == 0 (nrhip_gather_u8, nrhip_sort_u64, the Adam sweeps, a tensor of
+ * nrhip_adam_dense_tf_multi) or batch == 0 (the id arrays of nrhip_pairwise_mf_grad / nrhip_pointwise_mf_grad) the
+ * arrays of that length may be NULL — an empty device tensor has no storage. */
 int nrhip_rows_div(const int32_t* d_rows, int n_listed, int d, const float* d_src, float denom,
                    float* d_dst, void* stream);
 int nrhip_rows_clear(const int32_t* d_rows, int n_listed, int d, float* d_b0, float* d_b1,

@@ -490,7 +490,7 @@ int nrhip_device_info(int* cu_count, int* clock_khz, size_t* hbm_bytes, char* na
 
 int nrhip_adam_sparse_tf(float* d_var, float* d_m, float* d_v, float* d_grad, int64_t n,
                          float alpha, float beta1, float beta2, float eps, void* stream) {
-  NR_REQUIRE(d_var && d_m && d_v && d_grad && n >= 0, NR_ERR_ARG, "adam_sparse_tf: bad arguments");
+  NR_REQUIRE(n >= 0 && (n == 0 || (d_var && d_m && d_v && d_grad)), NR_ERR_ARG, "adam_sparse_tf: bad arguments");
   NR_REQUIRE(aligned16(d_var) && aligned16(d_m) && aligned16(d_v) && aligned16(d_grad), NR_ERR_ARG,
              "adam_sparse_tf: buffers must be 16-byte aligned");
   if (n == 0) return NR_OK;
@@ -534,7 +534,7 @@ int nrhip_adam_sparse_tf_lazy(float* d_var, float* d_m, float* d_v, float* d_gra
 int nrhip_adam_dense_tf(float* d_var, float* d_m, float* d_v, float* d_grad, int64_t n,
                         float alpha, float beta1, float beta2, float eps, int clear_grad,
                         void* stream) {
-  NR_REQUIRE(d_var && d_m && d_v && d_grad && n >= 0, NR_ERR_ARG, "adam_dense_tf: bad arguments");
+  NR_REQUIRE(n >= 0 && (n == 0 || (d_var && d_m && d_v && d_grad)), NR_ERR_ARG, "adam_dense_tf: bad arguments");
   NR_REQUIRE(aligned16(d_var) && aligned16(d_m) && aligned16(d_v) && aligned16(d_grad), NR_ERR_ARG,
              "adam_dense_tf: buffers must be 16-byte aligned");
   if (n == 0) return NR_OK;
@@ -578,7 +578,8 @@ int nrhip_adam_dense_tf_multi(int n_tensors, float* const* d_vars, float* const*
   MultiAdam t{};
   int64_t biggest = 0;
   for (int k = 0; k < n_tensors; ++k) {
-    NR_REQUIRE(d_vars[k] && d_ms[k] && d_vs[k] && d_grads[k] && sizes[k] >= 0, NR_ERR_ARG,
+    // an empty tensor has no storage: its pointers may be NULL
+    NR_REQUIRE(sizes[k] >= 0 && (sizes[k] == 0 || (d_vars[k] && d_ms[k] && d_vs[k] && d_grads[k])), NR_ERR_ARG,
                "adam_dense_tf_multi: tensor %d: bad arguments", k);
     NR_REQUIRE(aligned16(d_vars[k]) && aligned16(d_ms[k]) && aligned16(d_vs[k]) && aligned16(d_grads[k]),
                NR_ERR_ARG, "adam_dense_tf_multi: tensor %d: buffers must be 16-byte aligned", k);
@@ -595,7 +596,7 @@ int nrhip_adam_dense_tf_multi(int n_tensors, float* const* d_vars, float* const*
 
 int nrhip_rows_div(const int32_t* d_rows, int n_listed, int d, const float* d_src, float denom,
                    float* d_dst, void* stream) {
-  NR_REQUIRE(d_rows && d_src && d_dst && n_listed >= 0 && d >= 1, NR_ERR_ARG,
+  NR_REQUIRE(n_listed >= 0 && d >= 1 && (n_listed == 0 || (d_rows && d_src && d_dst)), NR_ERR_ARG,
              "rows_div: bad arguments");
   if (n_listed == 0) return NR_OK;
   hipLaunchKernelGGL(rows_div_kernel, dim3((n_listed + 3) / 4), dim3(256), 0, (hipStream_t)stream,
@@ -605,7 +606,7 @@ int nrhip_rows_div(const int32_t* d_rows, int n_listed, int d, const float* d_sr
 }
 
 int nrhip_gather_u8(const uint8_t* d_src, const int32_t* d_index, int64_t n, uint8_t* d_dst, void* stream) {
-  NR_REQUIRE(d_src && d_index && d_dst && n >= 0, NR_ERR_ARG, "gather_u8: bad arguments");
+  NR_REQUIRE(n >= 0 && (n == 0 || (d_src && d_index && d_dst)), NR_ERR_ARG, "gather_u8: bad arguments");
   if (n == 0) return NR_OK;
   hipLaunchKernelGGL(gather_u8_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_src,
                      d_index, n, d_dst);
@@ -614,7 +615,7 @@ int nrhip_gather_u8(const uint8_t* d_src, const int32_t* d_index, int64_t n, uin
 }
 
 int nrhip_mark_rows(const int32_t* d_ids, int n, int offset, uint8_t* d_flag, void* stream) {
-  NR_REQUIRE(d_ids && d_flag && n >= 0, NR_ERR_ARG, "mark_rows: bad arguments");
+  NR_REQUIRE(n >= 0 && (n == 0 || (d_ids && d_flag)), NR_ERR_ARG, "mark_rows: bad arguments");
   if (n == 0) return NR_OK;
   hipLaunchKernelGGL(mark_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                      d_ids, n, offset, d_flag);
@@ -674,7 +675,7 @@ int nrhip_optimizer_dense_tf(int kind, float* d_var, float* d_slot0, float* d_sl
 
 int nrhip_rows_gather(const int32_t* d_rows, int n_listed, int d, const float* d_src, float* d_dst,
                       int64_t ld_dst, void* stream) {
-  NR_REQUIRE(d_rows && d_src && d_dst && n_listed >= 0 && d >= 1 && ld_dst >= d, NR_ERR_ARG,
+  NR_REQUIRE(n_listed >= 0 && d >= 1 && ld_dst >= d && (n_listed == 0 || (d_rows && d_src && d_dst)), NR_ERR_ARG,
              "rows_gather: bad arguments");
   if (n_listed == 0) return NR_OK;
   hipLaunchKernelGGL(rows_gather_kernel, dim3((n_listed + 3) / 4), dim3(256), 0,
@@ -686,8 +687,8 @@ int nrhip_rows_gather(const int32_t* d_rows, int n_listed, int d, const float* d
 /* the same with a source row stride: d_src may be a column block of a wider row-major buffer */
 int nrhip_rows_gather_ld(const int32_t* d_rows, int n_listed, int d, const float* d_src, int64_t ld_src,
                          float* d_dst, int64_t ld_dst, void* stream) {
-  NR_REQUIRE(d_rows && d_src && d_dst && n_listed >= 0 && d >= 1 && ld_dst >= d && ld_src >= d, NR_ERR_ARG,
-             "rows_gather_ld: bad arguments");
+  NR_REQUIRE(n_listed >= 0 && d >= 1 && ld_dst >= d && ld_src >= d && (n_listed == 0 || (d_rows && d_src && d_dst)),
+             NR_ERR_ARG, "rows_gather_ld: bad arguments");
   if (n_listed == 0) return NR_OK;
   hipLaunchKernelGGL(rows_gather_kernel, dim3((n_listed + 3) / 4), dim3(256), 0,
                      (hipStream_t)stream, d_rows, n_listed, d, d_src, ld_src, d_dst, ld_dst);
@@ -699,8 +700,9 @@ int nrhip_rows_gather_ld(const int32_t* d_rows, int n_listed, int d, const float
 int nrhip_rows_gather2(const int32_t* d_rows, int n_listed, int d, const float* d_src_a, int64_t ld_a,
                        const float* d_src_b, int64_t ld_b, float* d_dst_a, int64_t ldd_a, float* d_dst_b,
                        int64_t ldd_b, void* stream) {
-  NR_REQUIRE(d_rows && d_src_a && d_src_b && d_dst_a && d_dst_b && n_listed >= 0 && d >= 1 && ld_a >= d && ld_b >= d &&
-                 ldd_a >= d && ldd_b >= d, NR_ERR_ARG, "rows_gather2: bad arguments");
+  NR_REQUIRE(n_listed >= 0 && d >= 1 && ld_a >= d && ld_b >= d && ldd_a >= d && ldd_b >= d &&
+                 (n_listed == 0 || (d_rows && d_src_a && d_src_b && d_dst_a && d_dst_b)),
+             NR_ERR_ARG, "rows_gather2: bad arguments");
   if (n_listed == 0) return NR_OK;
   hipLaunchKernelGGL(rows_gather2_kernel, dim3((n_listed + 3) / 4), dim3(256), 0, (hipStream_t)stream, d_rows,
                      n_listed, d, d_src_a, ld_a, d_src_b, ld_b, d_dst_a, ldd_a, d_dst_b, ldd_b);
@@ -710,7 +712,7 @@ int nrhip_rows_gather2(const int32_t* d_rows, int n_listed, int d, const float* 
 
 int nrhip_rows_scatter_add(const int32_t* d_rows, int n_listed, int d, const float* d_src,
                            int64_t ld_src, float* d_dst, void* stream) {
-  NR_REQUIRE(d_rows && d_src && d_dst && n_listed >= 0 && d >= 1 && ld_src >= d, NR_ERR_ARG,
+  NR_REQUIRE(n_listed >= 0 && d >= 1 && ld_src >= d && (n_listed == 0 || (d_rows && d_src && d_dst)), NR_ERR_ARG,
              "rows_scatter_add: bad arguments");
   if (n_listed == 0) return NR_OK;
   hipLaunchKernelGGL(rows_scatter_add_kernel, dim3((n_listed + 3) / 4), dim3(256), 0,
@@ -721,7 +723,7 @@ int nrhip_rows_scatter_add(const int32_t* d_rows, int n_listed, int d, const flo
 
 int nrhip_rows_clear(const int32_t* d_rows, int n_listed, int d, float* d_b0, float* d_b1,
                      float* d_b2, float* d_b3, uint8_t* d_flag, void* stream) {
-  NR_REQUIRE(d_rows && n_listed >= 0 && d >= 1, NR_ERR_ARG, "rows_clear: bad arguments");
+  NR_REQUIRE(n_listed >= 0 && d >= 1 && (n_listed == 0 || d_rows), NR_ERR_ARG, "rows_clear: bad arguments");
   if (n_listed == 0) return NR_OK;
   hipLaunchKernelGGL(rows_clear_kernel, dim3((n_listed + 3) / 4), dim3(256), 0,
                      (hipStream_t)stream, d_rows, n_listed, d, d_b0, d_b1, d_b2, d_b3, d_flag);

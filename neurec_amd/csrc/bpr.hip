@@ -1273,7 +1273,7 @@ int nrhip_bpr_plan(const int32_t* d_users, const int32_t* d_items, const int32_t
 /* In-place ascending sort of n 64-bit keys: one workgroup's LDS bitonic network up to 16384 keys, the
  * segmented multi-workgroup network beyond. */
 int nrhip_sort_u64(uint64_t* d_keys, int n, void* stream) {
-  NR_REQUIRE(d_keys && n >= 0, NR_ERR_ARG, "sort_u64: bad arguments");
+  NR_REQUIRE(n >= 0 && (n == 0 || d_keys), NR_ERR_ARG, "sort_u64: bad arguments");
   if (n <= 1) return NR_OK;
   if (n > kPlanMaxKeys) return sort_segments(d_keys, SegLayout{n, 0, 0}, 1, n, (hipStream_t)stream);
   NR_TRY(lds_attr_once((const void*)sort_u64_kernel, 1));
@@ -1363,7 +1363,8 @@ static int pairwise_mf_grad(const char* who, const float* d_P, const float* d_Q,
                             const int32_t* d_users, const int32_t* d_pos, const int32_t* d_neg,
                             int batch, float reg, int loss_kind, float* d_GP, float* d_GQ,
                             float* d_work, float* d_loss2, const uint64_t* d_plan, void* stream) {
-  NR_REQUIRE(d_P && d_Q && d_users && d_pos && d_neg && d_GP && d_GQ && d_work && d_loss2,
+  // an empty batch has no ids: its three id arrays may be NULL
+  NR_REQUIRE(d_P && d_Q && (batch == 0 || (d_users && d_pos && d_neg)) && d_GP && d_GQ && d_work && d_loss2,
              NR_ERR_ARG, "%s: null pointer argument", who);
   NR_REQUIRE(d >= 1 && d <= 256, NR_ERR_UNSUPPORTED, "%s: embedding dim %d outside 1..256", who, d);
   NR_REQUIRE(batch >= 0 && n_users >= 0, NR_ERR_ARG, "%s: negative batch / n_users", who);
@@ -1543,7 +1544,7 @@ int nrhip_pointwise_mf_grad(const float* d_P, const float* d_Q, int d, int n_use
                             const int32_t* d_users, const int32_t* d_items, const float* d_labels,
                             int batch, float reg, int loss_kind, float* d_GP, float* d_GQ,
                             float* d_work, float* d_loss2, const uint64_t* d_plan, void* stream) {
-  NR_REQUIRE(d_P && d_Q && d_users && d_items && d_labels && d_GP && d_GQ && d_work && d_loss2,
+  NR_REQUIRE(d_P && d_Q && (batch == 0 || (d_users && d_items && d_labels)) && d_GP && d_GQ && d_work && d_loss2,
              NR_ERR_ARG, "pointwise_mf_grad: null pointer argument");
   NR_REQUIRE(d >= 1 && d <= 256, NR_ERR_UNSUPPORTED,
              "pointwise_mf_grad: embedding dim %d outside 1..256", d);
