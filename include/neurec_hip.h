@@ -1530,6 +1530,67 @@ int nrhip_hrm_user_factors(const float* d_P, const float* d_V, int n_users, int 
                            int session_max, const int32_t* d_last, const int32_t* d_users, int batch, float* d_out,
                            int64_t ld, void* stream);
 
+/* ---- NPE (neural personalized embedding: ReLU-gated user, context and item embeddings) ------
+ * Replaces: NPE._create_inference / _create_loss / the optimizer's gradients (model/sequential_recommender/
+ * NPE.py:54-75) run by `sess.run((self.loss, self.optimizer), feed_dict)` (NPE.py:94-102).  These symbols are
+ * additions: no existing struct changes and NRHIP_ABI_VERSION stays 4.
+ * An instance is (user u, recents r_0..r_{L-1}, item i, label y) over d_P [n_users][d], d_V [n_items][d] (the
+ * reference's embeddings_IU) and d_W [n_items][d] (embeddings_IL, read only through the recents):
+ *     s = sum over l of W[r_l]   (added in l order)                                                  (NPE.py:59-61)
+ *     q = relu(P[u]) + relu(s)
+ *     x = sum over c of relu(V[i])_c q_c                                                             (NPE.py:62-64)
+ *     loss = pointwise_loss(kind, y, x) + reg l2_loss(P[u], V[i], W[r_.])                            (NPE.py:70-71)
+ * with l2_loss = sum(x^2) / 2 per occurrence and the loss kinds of nrhip_pointwise_mf_grad (the cross-entropy is the
+ * MEAN over `batch`).  The gates are strict, as TF's ReluGrad (features > 0): an input that is exactly 0, or -0,
+ * passes nothing.
+ * Batch: d_users, d_items, d_labels (float): `batch` entries each; d_recents int32 [batch][L].
+ * Output: d_loss2 = (loss term, regulariser term) of the tables as they come in; d_G_P / d_G_V / d_G_W: the rows the
+ * batch looked up are STORED (the others are left alone: keep them zero), each the sum of its occurrences' gradients
+ * in the order of its sort keys: a P or V row's occurrences by batch slot, a W row's by (slot, column).  d_flag_P /
+ * d_flag_V / d_flag_W (uint8 per table row, may be NULL): set to 1 for those rows (nrhip_optimizer_rows_tf).
+ * A slot whose user is no row of P or whose item or any recent is outside [0, n_items) takes no part.
+ * Work buffers: d_keys uint64 [batch (2 + L)], d_scal float [4 batch], d_s and d_ds float [batch][d] (the context sum
+ * and the already-gated derivative with respect to it); no [batch][L][d] block exists.
+ * The three tables share one key space: n_users + 2 n_items < 2^31 - 1; batch <= NRHIP_NPE_MAX_BATCH;
+ * d = 1..NRHIP_NPE_MAX_D, L = 1..NRHIP_NPE_MAX_ORDER (outside: NRHIP_ERR_UNSUPPORTED).  Every sum is taken in a fixed
+ * order, no floating-point atomics: two calls on the same inputs are bit-identical. */
+#define NRHIP_NPE_MAX_D 128
+#define NRHIP_NPE_MAX_ORDER 16 /* high_order; one lane per recent in the narrowest lane group */
+#define NRHIP_NPE_MAX_BATCH (1 << 24)
+typedef struct nrhip_npe_step_args {
+  const float* d_P;
+  const float* d_V;
+  const float* d_W;
+  float* d_G_P;
+  float* d_G_V;
+  float* d_G_W;
+  uint8_t* d_flag_P;
+  uint8_t* d_flag_V;
+  uint8_t* d_flag_W;
+  const int32_t* d_users;
+  const int32_t* d_recents;
+  const int32_t* d_items;
+  const float* d_labels;
+  uint64_t* d_keys;
+  float* d_scal;
+  float* d_s;
+  float* d_ds;
+  float* d_loss2;
+  int n_users, n_items, d, L, batch, loss_kind;
+  float reg;
+} nrhip_npe_step_args;
+int nrhip_npe_step(const nrhip_npe_step_args* args, void* stream);
+/* The evaluation's user factors: d_out [batch][ld] (ld >= d), row b = h_u = relu(P[u]) + relu(sum of W[last[u][l]])
+ * for u = d_users[b] (d_users NULL: u = b), so that its inner product with relu(V[i]) is predict()'s `output`
+ * (NPE.py:114-142).  d_last int32 [n_users][L]: -1 (or anything outside [0, n_items)): a slot that takes no part; with
+ * none h_u = relu(P[u]).  The sum and the gate are the step's own code.  A user outside [0, n_users) gets a row of
+ * zeros. */
+int nrhip_npe_user_factors(const float* d_P, const float* d_W, int n_users, int n_items, int d, int L,
+                           const int32_t* d_last, const int32_t* d_users, int batch, float* d_out, int64_t ld,
+                           void* stream);
+/* The evaluation's item factors: d_out [n_items][d] = relu(d_V), element for element. */
+int nrhip_npe_item_factors(const float* d_V, int n_items, int d, float* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -193,6 +193,14 @@ class HrmStepArgs(C.Structure):
         [("reg", C.c_float)]
 
 
+class NpeStepArgs(C.Structure):
+    """nrhip_npe_step_args (include/neurec_hip.h)"""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "P", "V", "W", "G_P", "G_V", "G_W", "flag_P", "flag_V", "flag_W", "users", "recents", "items", "labels",
+        "keys", "scal", "s", "ds", "loss2")] + \
+        [(n, C.c_int) for n in ("n_users", "n_items", "d", "L", "batch", "loss_kind")] + [("reg", C.c_float)]
+
+
 # name -> argtypes; every function returns int status except where noted.
 SIGNATURES = {
     "nrhip_device_info": [C.POINTER(i32), C.POINTER(i32), psz, C.c_char_p, i32],
@@ -383,6 +391,9 @@ SIGNATURES = {
     "nrhip_fossil_user_factors": [p, p, i32, i32, p, p, p, p, i32, i32, f32, p, i32, p, i64, p],
     "nrhip_hrm_step": [C.POINTER(HrmStepArgs), p],
     "nrhip_hrm_user_factors": [p, p, i32, i32, i32, i32, i32, i32, p, p, i32, p, i64, p],
+    "nrhip_npe_step": [C.POINTER(NpeStepArgs), p],
+    "nrhip_npe_user_factors": [p, p, i32, i32, i32, i32, p, p, i32, p, i64, p],
+    "nrhip_npe_item_factors": [p, i32, i32, p, p],
 }
 
 for _name, _args in SIGNATURES.items():

@@ -42,6 +42,9 @@ MODELS = {
             ("learning_rate", "0.001"), ("learner", "adam"), ("pre_agg", "max"), ("session_agg", "max"),
             ("high_order", "2"), ("num_neg", "4"), ("loss_function", "cross_entropy"), ("init_method", "normal"),
             ("stddev", "0.01"), ("verbose", "1")],
+    "NPE": [("epochs", "100"), ("batch_size", "256"), ("embedding_size", "64"), ("reg", "0.1"),
+            ("learning_rate", "0.001"), ("learner", "adam"), ("high_order", "3"), ("num_neg", "4"),
+            ("loss_function", "cross_entropy"), ("init_method", "tnormal"), ("stddev", "0.01"), ("verbose", "1")],
 }
 
 
