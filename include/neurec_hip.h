@@ -1076,7 +1076,10 @@ int nrhip_transpose2d(const float* d_src, int64_t ld_src, int rows, int cols, fl
                       void* stream);
 /* first encoder layer straight from the train CSR (tf.nn.l2_normalize + tf.nn.dropout + the first tf.matmul of
  * q_graph, MultiVAE.py:76-80): Y[b] = act(sum over the row's items of (1/sqrt(n)/keep*mask) * W[item] + bias);
- * d_h0val (per CSR position, optional) keeps the values for nrhip_vae_dwq0_wide */
+ * d_h0val (per CSR position, optional) keeps the values for nrhip_vae_dwq0_wide.  One grid row per batch row: this
+ * call and nrhip_vae_dwq0_wide take batch <= 65535 (above: NRHIP_ERR_UNSUPPORTED, nothing is launched).  The kernel
+ * entry points of this group and the row-wise ones of the NGCF group accept empty work (batch, n or rows = 0) with the
+ * NULL pointers of empty tensors; nrhip_gemm_f32 reads neither A nor B when K = 0. */
 int nrhip_vae_bag_fwd(const int64_t* d_indptr, const int32_t* d_indices, const int32_t* d_rows, int batch,
                       int width, const float* d_W, const float* d_bias, int act, float keep,
                       const float* d_drop_given, uint64_t seed, uint64_t step, float* d_h0val, float* d_Y,

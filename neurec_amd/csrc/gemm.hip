@@ -286,9 +286,10 @@ int nrhip_gemm_workspace_bytes(int M, int N, int splits, size_t* bytes) {
 int nrhip_gemm_f32(const float* d_A, int64_t lda, int a_kminor, const float* d_B, int64_t ldb, int b_kminor, int M,
                    int N, int K, float* d_C, int64_t ldc, int accumulate, const float* d_bias_n, int act, int splits,
                    void* d_ws, size_t ws_bytes, void* stream) {
-  NR_REQUIRE(d_A && d_B && d_C && M >= 0 && N >= 0 && K >= 0 && lda >= (a_kminor ? K : M) &&
-                 ldb >= (b_kminor ? K : N) && ldc >= N && lda < (1 << 24) && ldb < (1 << 24) && splits >= 1 &&
-                 act >= -1 && act <= 3, NR_ERR_ARG, "gemm_f32: bad arguments");
+  // (an empty tensor has no storage: C is required only when it has elements, A and B only when there is a product)
+  NR_REQUIRE(M >= 0 && N >= 0 && K >= 0 && lda >= (a_kminor ? K : M) && ldb >= (b_kminor ? K : N) && ldc >= N &&
+                 lda < (1 << 24) && ldb < (1 << 24) && splits >= 1 && act >= -1 && act <= 3 &&
+                 (M == 0 || N == 0 || (d_C && (K == 0 || (d_A && d_B)))), NR_ERR_ARG, "gemm_f32: bad arguments");
   // a k-minor operand is addressed from its first row through one buffer resource (2 GB window, 32-bit offsets)
   NR_REQUIRE((!a_kminor || (int64_t)M * lda * 4 < (1ll << 31)) && (!b_kminor || (int64_t)N * ldb * 4 < (1ll << 31)),
              NR_ERR_UNSUPPORTED, "gemm_f32: a k-minor operand of %lld bytes (limit 2 GB: give it k-major)",
@@ -376,8 +377,8 @@ int nrhip_gemm_kmajor(const float* d_A, int64_t lda, const float* d_B, int64_t l
 
 int nrhip_transpose2d(const float* d_src, int64_t ld_src, int rows, int cols, float* d_dst, int64_t ld_dst,
                       void* stream) {
-  NR_REQUIRE(d_src && d_dst && rows >= 0 && cols >= 0 && ld_src >= cols && ld_dst >= rows, NR_ERR_ARG,
-             "transpose2d: bad arguments");
+  NR_REQUIRE(rows >= 0 && cols >= 0 && ld_src >= cols && ld_dst >= rows && (rows == 0 || cols == 0 || (d_src && d_dst)),
+             NR_ERR_ARG, "transpose2d: bad arguments");
   if (rows == 0 || cols == 0) return NR_OK;
   hipLaunchKernelGGL(transpose2d_kernel, dim3((cols + 63) / 64, (rows + 63) / 64), dim3(256), 0,
                      (hipStream_t)stream, d_src, ld_src, rows, cols, d_dst, ld_dst);

@@ -201,8 +201,8 @@ extern "C" {
 
 int nrhip_ew_mul(const float* d_a, int64_t lda, const float* d_b, int64_t ldb, int64_t rows, int cols, float* d_out,
                  int64_t ldo, void* stream) {
-  NR_REQUIRE(d_a && d_b && d_out && rows >= 0 && cols >= 1 && lda >= cols && ldb >= cols && ldo >= cols, NR_ERR_ARG,
-             "ew_mul: bad arguments");
+  NR_REQUIRE(rows >= 0 && cols >= 1 && lda >= cols && ldb >= cols && ldo >= cols && (rows == 0 || (d_a && d_b && d_out)),
+             NR_ERR_ARG, "ew_mul: bad arguments");
   if (rows == 0) return NR_OK;
   hipLaunchKernelGGL(ew_mul_kernel, dim3((unsigned)((rows * cols + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      d_a, lda, d_b, ldb, rows, cols, d_out, ldo);
@@ -216,9 +216,11 @@ int nrhip_ew_mul(const float* d_a, int64_t lda, const float* d_b, int64_t ldb, i
 int nrhip_ngcf_act_fwd(const float* d_T1, const float* d_T2, int64_t ldt, int64_t n_rows, int w, int w_pad,
                        float keep, uint8_t* d_mask_io, int mask_given, uint64_t seed, uint64_t step, int layer,
                        float* d_ego_out, int64_t lde, float* d_out, int64_t ldo, void* stream) {
-  NR_REQUIRE(d_T1 && d_T2 && d_mask_io && d_ego_out && d_out && n_rows >= 0 && w >= 1 && w <= 64 * kMaxPer &&
-                 w_pad >= w && w_pad <= 64 * kMaxPer && ldt >= w && lde >= w_pad && ldo >= w && keep > 0.f &&
-                 keep <= 1.f, NR_ERR_ARG, "ngcf_act_fwd: bad arguments (widths 1..256)");
+  // (an empty tensor has no storage: the pointers are required only when there are rows)
+  NR_REQUIRE(n_rows >= 0 && w >= 1 && w <= 64 * kMaxPer && w_pad >= w && w_pad <= 64 * kMaxPer && ldt >= w &&
+                 lde >= w_pad && ldo >= w && keep > 0.f && keep <= 1.f &&
+                 (n_rows == 0 || (d_T1 && d_T2 && d_mask_io && d_ego_out && d_out)),
+             NR_ERR_ARG, "ngcf_act_fwd: bad arguments (widths 1..256)");
   if (n_rows == 0) return NR_OK;
   hipLaunchKernelGGL(ngcf_act_fwd_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
                      d_T1, d_T2, ldt, n_rows, w, w_pad, keep, d_mask_io, mask_given, seed, step, layer, d_ego_out, lde,
@@ -231,8 +233,9 @@ int nrhip_ngcf_act_bwd(const float* d_dout, int64_t ldo, const float* d_dego_nex
                        const float* d_ego_next, int64_t lde, const float* d_T1, const float* d_T2, int64_t ldt,
                        const uint8_t* d_mask, int64_t n_rows, int w, float keep, float* d_dT1, float* d_dT2,
                        void* stream) {
-  NR_REQUIRE(d_dout && d_ego_next && d_T1 && d_T2 && d_mask && d_dT1 && d_dT2 && n_rows >= 0 && w >= 1 &&
-                 w <= 64 * kMaxPer && ldo >= w && lde >= w && ldt >= w && (!d_dego_next || ldn >= w) && keep > 0.f,
+  NR_REQUIRE(n_rows >= 0 && w >= 1 && w <= 64 * kMaxPer && ldo >= w && lde >= w && ldt >= w &&
+                 (!d_dego_next || ldn >= w) && keep > 0.f &&
+                 (n_rows == 0 || (d_dout && d_ego_next && d_T1 && d_T2 && d_mask && d_dT1 && d_dT2)),
              NR_ERR_ARG, "ngcf_act_bwd: bad arguments (widths 1..256)");
   if (n_rows == 0) return NR_OK;
   hipLaunchKernelGGL(ngcf_act_bwd_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
@@ -245,8 +248,9 @@ int nrhip_ngcf_act_bwd(const float* d_dout, int64_t ldo, const float* d_dego_nex
 int nrhip_lrelu_drop_fwd(const float* d_T, int64_t ldt, int64_t n_rows, int w, int w_pad, float keep, uint8_t* d_mask_io,
                          int mask_given, uint64_t seed, uint64_t step, int layer, int flags, float* d_out_a, int64_t lda,
                          float* d_out_b, int64_t ldb, void* stream) {
-  NR_REQUIRE(d_T && (d_out_a || d_out_b) && n_rows >= 0 && w >= 1 && w_pad >= w && ldt >= w && (!d_out_a || lda >= w_pad) &&
-                 (!d_out_b || ldb >= w) && (!(flags & 2) || (d_mask_io && keep > 0.f && keep <= 1.f)), NR_ERR_ARG,
+  NR_REQUIRE(n_rows >= 0 && w >= 1 && w_pad >= w && ldt >= w && (!d_out_a || lda >= w_pad) && (!d_out_b || ldb >= w) &&
+                 (!(flags & 2) || (keep > 0.f && keep <= 1.f)) &&
+                 (n_rows == 0 || (d_T && (d_out_a || d_out_b) && (!(flags & 2) || d_mask_io))), NR_ERR_ARG,
              "lrelu_drop_fwd: bad arguments");
   if (n_rows == 0) return NR_OK;
   hipLaunchKernelGGL(lrelu_drop_fwd_kernel, dim3((unsigned)((n_rows * w_pad + 255) / 256)), dim3(256), 0,
@@ -258,8 +262,10 @@ int nrhip_lrelu_drop_fwd(const float* d_T, int64_t ldt, int64_t n_rows, int w, i
 
 int nrhip_lrelu_drop_bwd(const float* d_da, int64_t lda, const float* d_db, int64_t ldb, const float* d_T, int64_t ldt,
                          const uint8_t* d_mask, int64_t n_rows, int w, float keep, int flags, float* d_dT, void* stream) {
-  NR_REQUIRE(d_da && d_dT && n_rows >= 0 && w >= 1 && lda >= w && (!d_db || ldb >= w) && (!(flags & 1) || (d_T && ldt >= w)) &&
-                 (!(flags & 2) || (d_mask && keep > 0.f)), NR_ERR_ARG, "lrelu_drop_bwd: bad arguments");
+  NR_REQUIRE(n_rows >= 0 && w >= 1 && lda >= w && (!d_db || ldb >= w) && (!(flags & 1) || ldt >= w) &&
+                 (!(flags & 2) || keep > 0.f) &&
+                 (n_rows == 0 || (d_da && d_dT && (!(flags & 1) || d_T) && (!(flags & 2) || d_mask))), NR_ERR_ARG,
+             "lrelu_drop_bwd: bad arguments");
   if (n_rows == 0) return NR_OK;
   hipLaunchKernelGGL(lrelu_drop_bwd_kernel, dim3((unsigned)((n_rows * w + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      d_da, lda, d_db, ldb, d_T, ldt, d_mask, n_rows, w, keep, flags, d_dT);
@@ -269,7 +275,8 @@ int nrhip_lrelu_drop_bwd(const float* d_da, int64_t lda, const float* d_db, int6
 
 int nrhip_edge_dropout(const float* d_vals, int64_t n, float keep, uint8_t* d_keep_io, int given, uint64_t seed,
                        uint64_t step, float* d_out, void* stream) {
-  NR_REQUIRE(d_vals && d_keep_io && d_out && n >= 0 && keep > 0.f && keep <= 1.f, NR_ERR_ARG, "edge_dropout: bad arguments");
+  NR_REQUIRE(n >= 0 && keep > 0.f && keep <= 1.f && (n == 0 || (d_vals && d_keep_io && d_out)), NR_ERR_ARG,
+             "edge_dropout: bad arguments");
   if (n == 0) return NR_OK;
   hipLaunchKernelGGL(edge_dropout_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_vals, n,
                      keep, d_keep_io, given, seed, step, d_out);
@@ -278,7 +285,7 @@ int nrhip_edge_dropout(const float* d_vals, int64_t n, float keep, uint8_t* d_ke
 }
 
 int nrhip_gather_f32(const float* d_src, const int32_t* d_index, int64_t n, float* d_dst, void* stream) {
-  NR_REQUIRE(d_src && d_index && d_dst && n >= 0, NR_ERR_ARG, "gather_f32: bad arguments");
+  NR_REQUIRE(n >= 0 && (n == 0 || (d_src && d_index && d_dst)), NR_ERR_ARG, "gather_f32: bad arguments");
   if (n == 0) return NR_OK;
   hipLaunchKernelGGL(gather_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_src,
                      d_index, n, d_dst);
@@ -289,8 +296,9 @@ int nrhip_gather_f32(const float* d_src, const int32_t* d_index, int64_t n, floa
 int nrhip_ngcf_mix_bwd(const float* d_Y1, const float* d_Y2, int64_t ldy, const float* d_ego, const float* d_S,
                        int64_t lde, int64_t n_rows, int w, int w_pad, float* d_dS, float* d_dego_direct,
                        void* stream) {
-  NR_REQUIRE(d_Y1 && d_Y2 && d_ego && d_S && d_dS && d_dego_direct && n_rows >= 0 && w >= 1 && w_pad >= w &&
-                 ldy >= w && lde >= w_pad, NR_ERR_ARG, "ngcf_mix_bwd: bad arguments");
+  NR_REQUIRE(n_rows >= 0 && w >= 1 && w_pad >= w && ldy >= w && lde >= w_pad &&
+                 (n_rows == 0 || (d_Y1 && d_Y2 && d_ego && d_S && d_dS && d_dego_direct)), NR_ERR_ARG,
+             "ngcf_mix_bwd: bad arguments");
   if (n_rows == 0) return NR_OK;
   hipLaunchKernelGGL(ngcf_mix_bwd_kernel, dim3((unsigned)((n_rows * w_pad + 255) / 256)), dim3(256), 0,
                      (hipStream_t)stream, d_Y1, d_Y2, ldy, d_ego, d_S, lde, n_rows, w, w_pad, d_dS, d_dego_direct);

@@ -13,6 +13,7 @@
 namespace {
 
 enum { ACT_TANH = 0, ACT_SIGMOID = 1, ACT_RELU = 2, ACT_IDENTITY = 3 };
+constexpr int kMaxGridY = 65535;                             // grid.y of a launch: one grid row per batch row
 
 __device__ __forceinline__ float act_fwd(int a, float x) {
   if (a == ACT_TANH) return tanhf(x);
@@ -194,8 +195,12 @@ int nrhip_vae_bag_fwd(const int64_t* d_indptr, const int32_t* d_indices, const i
                       int width, const float* d_W, const float* d_bias, int act, float keep,
                       const float* d_drop_given, uint64_t seed, uint64_t step, float* d_h0val, float* d_Y,
                       void* stream) {
-  NR_REQUIRE(d_indptr && d_indices && d_rows && d_W && d_bias && d_Y && batch >= 0 && width >= 1 && act >= -1 &&
-                 act <= 3 && keep > 0.f && keep <= 1.f, NR_ERR_ARG, "vae_bag_fwd: bad arguments");
+  // (an empty tensor has no storage: the per-row pointers are required only when there are rows)
+  NR_REQUIRE(batch >= 0 && width >= 1 && act >= -1 && act <= 3 && keep > 0.f && keep <= 1.f &&
+                 (batch == 0 || (d_indptr && d_indices && d_rows && d_W && d_bias && d_Y)), NR_ERR_ARG,
+             "vae_bag_fwd: bad arguments");
+  NR_REQUIRE(batch <= kMaxGridY, NR_ERR_UNSUPPORTED, "vae_bag_fwd: batch %d (one grid row per batch row: at most %d)",
+             batch, kMaxGridY);
   if (batch == 0) return NR_OK;
   hipLaunchKernelGGL(vae_bag_fwd_kernel, dim3((width + 255) / 256, batch), dim3(256), 0, (hipStream_t)stream, d_indptr,
                      d_indices, d_rows, batch, width, d_W, d_bias, act, keep, d_drop_given, seed, step, d_h0val, d_Y);
@@ -204,7 +209,7 @@ int nrhip_vae_bag_fwd(const int64_t* d_indptr, const int32_t* d_indices, const i
 }
 
 int nrhip_act_bwd(const float* d_dY, const float* d_Y, int64_t n, int act, float* d_dA, void* stream) {
-  NR_REQUIRE(d_dY && d_Y && d_dA && n >= 0 && act >= 0 && act <= 3, NR_ERR_ARG, "act_bwd: bad arguments");
+  NR_REQUIRE(n >= 0 && act >= 0 && act <= 3 && (n == 0 || (d_dY && d_Y && d_dA)), NR_ERR_ARG, "act_bwd: bad arguments");
   if (n == 0) return NR_OK;
   hipLaunchKernelGGL(act_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_dY, d_Y,
                      n, act, d_dA);
@@ -214,7 +219,8 @@ int nrhip_act_bwd(const float* d_dY, const float* d_Y, int64_t n, int act, float
 
 int nrhip_vae_sample(const float* d_H2, int batch, int z, const float* d_eps_given, float is_training, uint64_t seed,
                      uint64_t step, float* d_EPSSTD, float* d_ZS, float* d_KLb, void* stream) {
-  NR_REQUIRE(d_H2 && d_EPSSTD && d_ZS && d_KLb && batch >= 0 && z >= 1, NR_ERR_ARG, "vae_sample: bad arguments");
+  NR_REQUIRE(batch >= 0 && z >= 1 && (batch == 0 || (d_H2 && d_EPSSTD && d_ZS && d_KLb)), NR_ERR_ARG,
+             "vae_sample: bad arguments");
   if (batch == 0) return NR_OK;
   hipLaunchKernelGGL(vae_sample_kernel, dim3((batch + 3) / 4), dim3(256), 0, (hipStream_t)stream, d_H2, batch, z,
                      d_eps_given, is_training, seed, step, d_EPSSTD, d_ZS, d_KLb);
@@ -224,7 +230,8 @@ int nrhip_vae_sample(const float* d_H2, int batch, int z, const float* d_eps_giv
 
 int nrhip_vae_sample_bwd(const float* d_dZ, const float* d_H2, const float* d_EPSSTD, int batch, int z, float anneal,
                          float* d_dH2, void* stream) {
-  NR_REQUIRE(d_dZ && d_H2 && d_EPSSTD && d_dH2 && batch >= 0 && z >= 1, NR_ERR_ARG, "vae_sample_bwd: bad arguments");
+  NR_REQUIRE(batch >= 0 && z >= 1 && (batch == 0 || (d_dZ && d_H2 && d_EPSSTD && d_dH2)), NR_ERR_ARG,
+             "vae_sample_bwd: bad arguments");
   if (batch == 0) return NR_OK;
   hipLaunchKernelGGL(vae_sample_bwd_kernel, dim3((unsigned)(((int64_t)batch * z + 255) / 256)), dim3(256), 0,
                      (hipStream_t)stream, d_dZ, d_H2, d_EPSSTD, batch, z, anneal, d_dH2);
@@ -235,8 +242,8 @@ int nrhip_vae_sample_bwd(const float* d_dZ, const float* d_H2, const float* d_EP
 /* logits slab S[batch][ld] (cols valid) -> d_nll[b] and, IN PLACE, dLoss/dlogits = (softmax * n_b - x) / batch */
 int nrhip_vae_softmax_dlogits(float* d_S, int64_t ld, int batch, int cols, const int64_t* d_indptr,
                               const int32_t* d_indices, const int32_t* d_rows, float* d_nll, void* stream) {
-  NR_REQUIRE(d_S && d_indptr && d_indices && d_rows && d_nll && batch >= 0 && cols >= 1 && ld >= cols, NR_ERR_ARG,
-             "vae_softmax_dlogits: bad arguments");
+  NR_REQUIRE(batch >= 0 && cols >= 1 && ld >= cols && (batch == 0 || (d_S && d_indptr && d_indices && d_rows && d_nll)),
+             NR_ERR_ARG, "vae_softmax_dlogits: bad arguments");
   if (batch == 0) return NR_OK;
   hipLaunchKernelGGL(vae_softmax_dlogits_kernel, dim3(batch), dim3(1024), 0, (hipStream_t)stream, d_S, ld, cols,
                      d_indptr, d_indices, d_rows, batch, d_nll);
@@ -246,8 +253,11 @@ int nrhip_vae_softmax_dlogits(float* d_S, int64_t ld, int batch, int cols, const
 
 int nrhip_vae_dwq0_wide(const int64_t* d_indptr, const int32_t* d_indices, const int32_t* d_rows, int batch,
                         int width, const float* d_h0val, const float* d_DA1, float* d_dWq0, void* stream) {
-  NR_REQUIRE(d_indptr && d_indices && d_rows && d_h0val && d_DA1 && d_dWq0 && batch >= 0 && width >= 1, NR_ERR_ARG,
+  NR_REQUIRE(batch >= 0 && width >= 1 &&
+                 (batch == 0 || (d_indptr && d_indices && d_rows && d_h0val && d_DA1 && d_dWq0)), NR_ERR_ARG,
              "vae_dwq0_wide: bad arguments");
+  NR_REQUIRE(batch <= kMaxGridY, NR_ERR_UNSUPPORTED, "vae_dwq0_wide: batch %d (one grid row per batch row: at most %d)",
+             batch, kMaxGridY);
   if (batch == 0) return NR_OK;
   hipLaunchKernelGGL(vae_dwq0_wide_kernel, dim3((width + 255) / 256, batch), dim3(256), 0, (hipStream_t)stream, d_indptr,
                      d_indices, d_rows, batch, width, d_h0val, d_DA1, d_dWq0);
@@ -284,7 +294,9 @@ __global__ __launch_bounds__(1024) void colsum_rows_kernel(const float* __restri
 /* d_out[c] = sum_r d_X[r][c] (bias gradients).  rows > 2048 needs d_ws of ceil(rows / 512) * cols floats. */
 extern "C" int nrhip_colsum_rows(const float* d_X, int64_t ld, int rows, int cols, float* d_out, void* d_ws,
                                  size_t ws_bytes, void* stream) {
-  NR_REQUIRE(d_X && d_out && rows >= 0 && cols >= 1 && ld >= cols, NR_ERR_ARG, "colsum_rows: bad arguments");
+  // (rows == 0 reads nothing of d_X — an empty tensor's NULL — and writes zeros)
+  NR_REQUIRE(d_out && rows >= 0 && cols >= 1 && ld >= cols && (rows == 0 || d_X), NR_ERR_ARG,
+             "colsum_rows: bad arguments");
   hipStream_t st = (hipStream_t)stream;
   const unsigned bx = (unsigned)((cols + 63) / 64);
   if (rows <= 2048) {
