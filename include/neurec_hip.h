@@ -1594,6 +1594,97 @@ int nrhip_npe_user_factors(const float* d_P, const float* d_W, int n_users, int 
 /* The evaluation's item factors: d_out [n_items][d] = relu(d_V), element for element. */
 int nrhip_npe_item_factors(const float* d_V, int n_items, int d, float* d_out, void* stream);
 
+/* ---- FPMCplus (FPMC with an attention MLP over the user's last high_order items, per target item) ------
+ * nrhip_fpmcplus_step replaces: FPMCplus._attention_mlp / _create_inference / _create_loss / the optimizer's gradients
+ * (model/sequential_recommender/FPMCplus.py:73-119) run by `sess.run((self.loss, self.optimizer), feed_dict)`
+ * (FPMCplus.py:154, 164).  nrhip_fpmcplus_scores replaces predict() (FPMCplus.py:177-205).  These symbols are
+ * additions: no existing struct changes and NRHIP_ABI_VERSION stays 4.
+ * An instance is (user u, recents r_0..r_{L-1}, item i[, negative j]) over d_UI [n_users][d], d_IU / d_IL / d_LI
+ * [n_items][d], d_W [3 d][w] = [W_u; W_i; W_l], d_b [w], d_h [w]:
+ *     a_l[k] = tanh(UI[u] . W_u[:,k] + IL[i] . W_i[:,k] + LI[r_l] . W_l[:,k] + b[k])            (FPMCplus.py:75-82)
+ *     A_l = sum_k a_l[k] h[k];  alpha_l = exp(A_l) / sum_m exp(A_m)  (no max subtracted)          (FPMCplus.py:85-91)
+ *     x(u, i) = <UI[u], IU[i]> + <IL[i], sum_l alpha_l LI[r_l]>                                   (FPMCplus.py:93-105)
+ *     pairwise:  loss = pairwise_loss(kind, x(u,i) - x(u,j)) + reg_mf l2_loss(UI_u, IU_i, IL_i, LI_l, IU_j, IL_j)
+ *                       + reg_w l2_loss(W, h)                                                     (FPMCplus.py:111-116)
+ *     pointwise: loss = pointwise_loss(kind, y, x(u,i)) + reg_mf l2_loss(UI_u, IU_i, IL_i, LI_l)  (FPMCplus.py:118-119)
+ * with l2_loss = sum(x^2) / 2 per occurrence and the loss kinds of nrhip_pairwise_mf_grad / nrhip_pointwise_mf_grad
+ * (the cross-entropy is the MEAN over `batch`).  Pointwise mode has no reg_w term and b is never regularised, as the
+ * class has it.  d_third: int32 negatives (pairwise) or float labels.
+ * Stores (does not add) d_G_UI / d_G_IU / d_G_IL / d_G_LI rows of every looked-up row (each row's occurrences summed
+ * along its run of the sorted keys, the regulariser's share per occurrence) and d_G_W / d_G_b / d_G_h whole (per-chunk
+ * partials, then one ordered pass); sets d_flag_* (any may be NULL) of the looked-up rows; d_loss2 = (loss term,
+ * regulariser term).  A slot whose user or item (or negative) is no table row takes no part; a RECENT outside
+ * [0, n_items) takes no part in the softmax or in any gradient while the rest of its instance does (none present:
+ * x = <UI[u], IU[i]>).
+ * Work buffers, K = (pairwise ? 5 : 3) + L: d_keys uint64 [K batch], d_contrib float [K batch][d] (one gradient row per
+ * lookup), d_scal float [4 batch], d_delta float [batch][(L + 4) w], d_partial float
+ * [NRHIP_FPMCPLUS_MAX_CHUNKS][3 d w + 2 w].
+ * The four tables share one key space: n_users + 3 n_items < 2^31 - 1; batch <= NRHIP_FPMCPLUS_MAX_BATCH; batch == 0
+ * launches nothing, writes nothing and needs no pointer.  d = 1..NRHIP_FPMCPLUS_MAX_D, w = 1..NRHIP_FPMCPLUS_MAX_W,
+ * L = 1..NRHIP_FPMCPLUS_MAX_L (outside: NRHIP_ERR_UNSUPPORTED).  Every sum is taken in a fixed order, no floating-point
+ * atomics: two calls on the same inputs are bit-identical. */
+#define NRHIP_FPMCPLUS_MAX_D 128
+#define NRHIP_FPMCPLUS_MAX_W 64
+#define NRHIP_FPMCPLUS_MAX_L 16
+#define NRHIP_FPMCPLUS_MAX_BATCH (1 << 22)
+#define NRHIP_FPMCPLUS_MAX_CHUNKS 64   /* partial sums of the dense gradients: min(ceil(batch / 32), this) chunks */
+#define NRHIP_FPMCPLUS_SCORE_USERS 256 /* users a workgroup of nrhip_fpmcplus_scores walks per item tile */
+typedef struct nrhip_fpmcplus_step_args {
+  const float* d_UI;
+  const float* d_IU;
+  const float* d_IL;
+  const float* d_LI;
+  const float* d_W;
+  const float* d_b;
+  const float* d_h;
+  float* d_G_UI;
+  float* d_G_IU;
+  float* d_G_IL;
+  float* d_G_LI;
+  float* d_G_W;
+  float* d_G_b;
+  float* d_G_h;
+  uint8_t* d_flag_UI;
+  uint8_t* d_flag_IU;
+  uint8_t* d_flag_IL;
+  uint8_t* d_flag_LI;
+  const int32_t* d_users;
+  const int32_t* d_recents; /* [batch][L] */
+  const int32_t* d_items;
+  const void* d_third;
+  uint64_t* d_keys;
+  float* d_contrib;
+  float* d_scal;
+  float* d_delta;
+  float* d_partial;
+  float* d_loss2;
+  int n_users, n_items, d, w, L, batch, pairwise, loss_kind;
+  float reg_mf, reg_w;
+} nrhip_fpmcplus_step_args;
+int nrhip_fpmcplus_step(const nrhip_fpmcplus_step_args* args, void* stream);
+/* predict(): d_out [batch][ld] (ld >= n_items), row n = x(u, i) for u = d_users[n] and every item i, the recents of u
+ * the row d_last [n_users][L] (-1, or anything outside [0, n_items): a slot that takes no part; the softmax covers the
+ * present slots alone; none: x = <UI[u], IU[i]>).  A user outside [0, n_users) gets a row of zeros.
+ * Work buffers: d_c float [batch][L][w] and d_p float [n_items][w], the user-side and item-side halves of the
+ * pre-activation; nothing of size batch x n_items x L exists. */
+typedef struct nrhip_fpmcplus_scores_args {
+  const float* d_UI;
+  const float* d_IU;
+  const float* d_IL;
+  const float* d_LI;
+  const float* d_W;
+  const float* d_b;
+  const float* d_h;
+  const int32_t* d_last;
+  const int32_t* d_users;
+  float* d_c;
+  float* d_p;
+  float* d_out;
+  int64_t ld;
+  int n_users, n_items, d, w, L, batch;
+} nrhip_fpmcplus_scores_args;
+int nrhip_fpmcplus_scores(const nrhip_fpmcplus_scores_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -201,6 +201,23 @@ class NpeStepArgs(C.Structure):
         [(n, C.c_int) for n in ("n_users", "n_items", "d", "L", "batch", "loss_kind")] + [("reg", C.c_float)]
 
 
+class FpmcplusStepArgs(C.Structure):
+    """nrhip_fpmcplus_step_args (include/neurec_hip.h)"""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "UI", "IU", "IL", "LI", "W", "b", "h", "G_UI", "G_IU", "G_IL", "G_LI", "G_W", "G_b", "G_h", "flag_UI",
+        "flag_IU", "flag_IL", "flag_LI", "users", "recents", "items", "third", "keys", "contrib", "scal", "delta",
+        "partial", "loss2")] + \
+        [(n, C.c_int) for n in ("n_users", "n_items", "d", "w", "L", "batch", "pairwise", "loss_kind")] + \
+        [("reg_mf", C.c_float), ("reg_w", C.c_float)]
+
+
+class FpmcplusScoresArgs(C.Structure):
+    """nrhip_fpmcplus_scores_args (include/neurec_hip.h)"""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "UI", "IU", "IL", "LI", "W", "b", "h", "last", "users", "c", "p", "out")] + [("ld", C.c_int64)] + \
+        [(n, C.c_int) for n in ("n_users", "n_items", "d", "w", "L", "batch")]
+
+
 # name -> argtypes; every function returns int status except where noted.
 SIGNATURES = {
     "nrhip_device_info": [C.POINTER(i32), C.POINTER(i32), psz, C.c_char_p, i32],
@@ -394,6 +411,8 @@ SIGNATURES = {
     "nrhip_npe_step": [C.POINTER(NpeStepArgs), p],
     "nrhip_npe_user_factors": [p, p, i32, i32, i32, i32, p, p, i32, p, i64, p],
     "nrhip_npe_item_factors": [p, i32, i32, p, p],
+    "nrhip_fpmcplus_step": [C.POINTER(FpmcplusStepArgs), p],
+    "nrhip_fpmcplus_scores": [C.POINTER(FpmcplusScoresArgs), p],
 }
 
 for _name, _args in SIGNATURES.items():

@@ -45,6 +45,11 @@ MODELS = {
     "NPE": [("epochs", "100"), ("batch_size", "256"), ("embedding_size", "64"), ("reg", "0.1"),
             ("learning_rate", "0.001"), ("learner", "adam"), ("high_order", "3"), ("num_neg", "4"),
             ("loss_function", "cross_entropy"), ("init_method", "tnormal"), ("stddev", "0.01"), ("verbose", "1")],
+    "FPMCplus": [("epochs", "500"), ("batch_size", "128"), ("embedding_size", "16"), ("weight_size", "16"),
+                 ("high_order", "3"), ("reg_mf", "0.00001"), ("reg_w", "0.001"), ("learning_rate", "0.001"),
+                 ("learner", "adam"), ("is_pairwise", "True"), ("num_neg", "4"), ("loss_function", "BPR"),
+                 ("embed_init_method", "tnormal"), ("weight_init_method", "he_normal"), ("stddev", "0.01"),
+                 ("verbose", "1")],
 }
 
 
