@@ -1685,6 +1685,77 @@ typedef struct nrhip_fpmcplus_scores_args {
 } nrhip_fpmcplus_scores_args;
 int nrhip_fpmcplus_scores(const nrhip_fpmcplus_scores_args* args, void* stream);
 
+/* ---- TransRec (translation-based recommendation: one item table in three roles, a dense translation vector) ------
+ * nrhip_transrec_step replaces: TransRec._create_inference / _create_loss / the optimizer's gradients
+ * (model/sequential_recommender/TransRec.py:66-95) run by `sess.run((self.loss, self.optimizer), feed_dict)`
+ * (TransRec.py:131, 140).  These symbols are additions: no existing struct changes and NRHIP_ABI_VERSION stays 4.
+ * An instance is (user u, recent item l, item i[, negative j]); P [n_users][d], Q [n_items][d], b [n_items], T [d]:
+ *     v = P[u] + T + Q[l] - Q[i];   x(u, l, i) = b[i] - |v|^2   (the SQUARED distance)             (TransRec.py:75-77)
+ *     pointwise (d_third = float labels)    loss = pointwise_loss(kind, label, x(u,l,i))
+ *                                                  + reg l2_loss(P[u], Q[l], Q[i], b[i], T)               (TransRec.py:90-91)
+ *     pairwise  (d_third = int32 negatives) loss = pairwise_loss(kind, x(u,l,i) - x(u,l,j))
+ *                                                  + reg l2_loss(P[u], Q[l], Q[j], Q[i], b[i], b[j], T)   (TransRec.py:87-88)
+ * with l2_loss = sum(x^2) / 2 and the loss kinds of nrhip_pointwise_mf_grad / nrhip_pairwise_mf_grad (the pointwise
+ * cross-entropy is the MEAN over `batch`).  P[u] and Q[l] are regularised once per instance although the pairwise graph
+ * looks them up in both inferences; T once per STEP.
+ * Output: d_loss2 = (loss term, regulariser term) of the tables as they come in.  d_G_P [n_users][d], d_G_Q
+ * [n_items][d]: the rows the batch looked up are STORED (the others are left alone: keep them zero), each the sum of
+ * its occurrences' gradients — Q's over its occurrences as recent item, target and negative — in the order of the sorted
+ * keys: by position in the batch, the first inference's lookups (positions 0..batch) before the second's
+ * (batch..2 batch), at one position the recent item before the target / negative.  d_G_b [n_items]: stored for the
+ * items that are a target or a negative (+-g + reg b per occurrence); an item that is a recent item only is left
+ * alone.  d_G_T [d]: stored whole, the instances' sum in chunks of the batch plus reg T.  d_flag_P / d_flag_Q /
+ * d_flag_b (uint8 per row, may be NULL): set to 1 for the rows nrhip_optimizer_rows_tf is to move.
+ * A slot whose user is no row of P or whose recent item, item or negative is outside [0, n_items) takes no part.
+ * Work buffers: d_keys uint64 [3 N] for N = batch (pointwise) or 2 batch (pairwise), d_scal float [4 batch],
+ * d_partial float [min(ceil(batch / NRHIP_TRANSREC_CHUNK), NRHIP_TRANSREC_MAX_CHUNKS)][d].
+ * n_users + n_items < 2^31 - 1; batch <= NRHIP_TRANSREC_MAX_BATCH; batch == 0 launches nothing, writes nothing and
+ * needs no pointer; d = 1..NRHIP_TRANSREC_MAX_D (outside: NRHIP_ERR_UNSUPPORTED).  Every sum is taken in a fixed
+ * order, no floating-point atomics: two calls on the same inputs are bit-identical. */
+#define NRHIP_TRANSREC_MAX_D 128
+#define NRHIP_TRANSREC_MAX_BATCH (1 << 24)
+#define NRHIP_TRANSREC_CHUNK 32        /* instances per partial sum of G_T while there are at most MAX_CHUNKS chunks */
+#define NRHIP_TRANSREC_MAX_CHUNKS 64
+typedef struct nrhip_transrec_step_args {
+  const float* d_P;
+  const float* d_Q;
+  const float* d_b;
+  const float* d_T;
+  float* d_G_P;
+  float* d_G_Q;
+  float* d_G_b;
+  float* d_G_T;
+  uint8_t* d_flag_P;
+  uint8_t* d_flag_Q;
+  uint8_t* d_flag_b;
+  const int32_t* d_users;
+  const int32_t* d_recent;
+  const int32_t* d_items;
+  const void* d_third;
+  uint64_t* d_keys;
+  float* d_scal;
+  float* d_partial;
+  float* d_loss2;
+  int n_users, n_items, d, batch, pairwise, loss_kind;
+  float reg;
+} nrhip_transrec_step_args;
+int nrhip_transrec_step(const nrhip_transrec_step_args* args, void* stream);
+/* Replaces the query side of TransRec's prediction graph, `u_emb + global_embedding + last_i_emb` (TransRec.py:102-104):
+ * d_out [batch][ld] (ld >= d), row n = P[u] + T + Q[d_last[u]] for u = d_users[n] (d_users NULL: u = n).  d_last int32
+ * [n_users]: the user's most recent train item; -1 (or anything outside [0, n_items)): none — the row is P[u] + T.  A
+ * user outside [0, n_users) gets a row of zeros. */
+int nrhip_transrec_queries(const float* d_P, const float* d_Q, const float* d_T, int n_users, int n_items, int d,
+                           const int32_t* d_last, const int32_t* d_users, int batch, float* d_out, int64_t ld,
+                           void* stream);
+/* Replaces `-l2_distance(pre_emb, j_emb) + item_biases` (TransRec.py:18-19, 105-107) and the per-batch
+ * `sess.run(self.prediction)` of predict() (TransRec.py:153-161): d_out [n][ld] (ld >= n_items; the columns beyond
+ * n_items are left alone), d_out[r][j] = d_b[j] - sqrt(sum_c (d_q[r][c] - d_Q[j][c])^2) for the query rows d_q [n][ldq]
+ * (ldq >= d).  The DIRECT form: per output the difference, then a fused multiply-accumulate in fp32, columns
+ * ascending; the expanded form |q|^2 + |Q_j|^2 - 2 q.Q_j cancels worst for the items nearest the query.  n, n_items
+ * and d need not be multiples of anything; n <= 65535 * 64. */
+int nrhip_transrec_scores(const float* d_q, int64_t ldq, const float* d_Q, const float* d_b, int n, int n_items, int d,
+                          float* d_out, int64_t ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

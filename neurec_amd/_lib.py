@@ -218,6 +218,14 @@ class FpmcplusScoresArgs(C.Structure):
         [(n, C.c_int) for n in ("n_users", "n_items", "d", "w", "L", "batch")]
 
 
+class TransrecStepArgs(C.Structure):
+    """nrhip_transrec_step_args (include/neurec_hip.h)"""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "P", "Q", "b", "T", "G_P", "G_Q", "G_b", "G_T", "flag_P", "flag_Q", "flag_b", "users", "recent", "items",
+        "third", "keys", "scal", "partial", "loss2")] + \
+        [(n, C.c_int) for n in ("n_users", "n_items", "d", "batch", "pairwise", "loss_kind")] + [("reg", C.c_float)]
+
+
 # name -> argtypes; every function returns int status except where noted.
 SIGNATURES = {
     "nrhip_device_info": [C.POINTER(i32), C.POINTER(i32), psz, C.c_char_p, i32],
@@ -413,6 +421,9 @@ SIGNATURES = {
     "nrhip_npe_item_factors": [p, i32, i32, p, p],
     "nrhip_fpmcplus_step": [C.POINTER(FpmcplusStepArgs), p],
     "nrhip_fpmcplus_scores": [C.POINTER(FpmcplusScoresArgs), p],
+    "nrhip_transrec_step": [C.POINTER(TransrecStepArgs), p],
+    "nrhip_transrec_queries": [p, p, p, i32, i32, i32, p, p, i32, p, i64, p],
+    "nrhip_transrec_scores": [p, i64, p, p, i32, i32, i32, p, i64, p],
 }
 
 for _name, _args in SIGNATURES.items():

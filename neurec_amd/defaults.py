@@ -50,6 +50,9 @@ MODELS = {
                  ("learner", "adam"), ("is_pairwise", "True"), ("num_neg", "4"), ("loss_function", "BPR"),
                  ("embed_init_method", "tnormal"), ("weight_init_method", "he_normal"), ("stddev", "0.01"),
                  ("verbose", "1")],
+    "TransRec": [("epochs", "500"), ("batch_size", "1024"), ("embedding_size", "50"), ("reg_mf", "0.0"),
+                 ("learning_rate", "0.001"), ("learner", "adam"), ("is_pairwise", "True"), ("num_neg", "4"),
+                 ("loss_function", "bpr"), ("init_method", "tnormal"), ("stddev", "0.01"), ("verbose", "1")],
 }
 
 
