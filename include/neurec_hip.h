@@ -1756,6 +1756,87 @@ int nrhip_transrec_queries(const float* d_P, const float* d_Q, const float* d_T,
 int nrhip_transrec_scores(const float* d_q, int64_t ldq, const float* d_Q, const float* d_b, int n, int n_items, int d,
                           float* d_out, int64_t ld, void* stream);
 
+/* ---- GRU4Rec (session-based recommendation with a stack of GRU cells; state carried across steps) ---------------
+ * These symbols are additions: no existing struct changes and NRHIP_ABI_VERSION stays 4.
+ * Variables: E_in [n_items][n_0], Q [n_items][n_last], b [n_items] (GRU4Rec.py:80-85) and per layer l, with input
+ * width in_0 = n_0, in_l = n_(l-1): Wg_l [in_l + n_l][2 n_l], bg_l [2 n_l], Wc_l [in_l + n_l][n_l], bc_l [n_l]
+ * (the variables of tf.nn.rnn_cell.GRUCell, GRU4Rec.py:111).  The cell [EXT: tensorflow r1.12 rnn_cell_impl.GRUCell]:
+ *     [r, u] = sigmoid([x, s] Wg + bg)  (r the first n_l columns);  c = act([x, r * s] Wc + bc);  h = u s + (1 - u) c
+ * nrhip_gru4rec_step replaces one `sess.run([self.update_opt, self.final_state], feed)` of GRU4Rec.py:160 up to the
+ * optimiser: the graph of GRU4Rec.py:111-131 forward, the loss (GRU4Rec.py:87-101) and every gradient.  The states
+ * d_state[l] [batch][n_l] are constants (placeholders, GRU4Rec.py:77: nothing flows back through them).
+ *     x = E_in[X];  h_top = the stack's output;  Z[i][j] = h_top[i] . Q[Y[j]] + b[Y[j]];  A = final_act(Z)
+ *     bpr   mean over all batch^2 entries of -log_sigmoid(A[i][i] - A[i][j])                       (GRU4Rec.py:87-92)
+ *     top1  mean_i (mean_j sigmoid(A[i][j] - A[i][i]) + mean_j sigmoid(A[i][j]^2) - sigmoid(A[i][i]^2) / batch)
+ *                                                                                                    (GRU4Rec.py:94-101)
+ *     + reg (l2(E_in[X]) + l2(Q[Y]) + l2(b[Y])), l2 = sum of squares / 2, on the GATHERED rows      (GRU4Rec.py:130-131)
+ * hidden_act: 0 tanh, 1 relu.  final_act: 0 linear, 1 relu, 2 leaky_relu (alpha 0.2).  loss_kind: 0 top1, 1 bpr.
+ * Output: d_loss2 = (loss term, reg * regulariser sum); d_h_new[l] [batch][n_l] the new states; d_G_Wg / d_G_bg /
+ * d_G_Wc / d_G_bc stored whole, every element the batch's sum in slot order; the rows of d_G_Ein the batch read and
+ * the rows of d_G_Q / d_G_b it scored are STORED (the others are left alone: keep them zero), a row that occurs more
+ * than once as the sum of its slots along a run of sorted keys (item << 32 | slot), slot order.  A slot whose X (Y)
+ * is outside [0, n_items) reads a row of zeros and its gradient row is dropped.
+ * Work buffers: d_keys uint64 [2 batch]; d_ws float [nrhip_gru4rec_workspace_floats].  1..NRHIP_GRU4REC_MAX_LAYERS
+ * layers of width 1..NRHIP_GRU4REC_MAX_WIDTH (outside: NRHIP_ERR_UNSUPPORTED); batch <= NRHIP_GRU4REC_MAX_BATCH;
+ * batch == 0 launches nothing and writes nothing.  fp32 throughout, every sum in a fixed order, no atomics: two calls
+ * on the same inputs are bit-identical. */
+#define NRHIP_GRU4REC_MAX_LAYERS 3
+#define NRHIP_GRU4REC_MAX_WIDTH 128
+#define NRHIP_GRU4REC_MAX_BATCH 4096
+#define NRHIP_GRU4REC_TILE 16          /* users per workgroup of nrhip_gru4rec_user_states */
+typedef struct nrhip_gru4rec_weights {
+  const float* d_Wg[NRHIP_GRU4REC_MAX_LAYERS];
+  const float* d_bg[NRHIP_GRU4REC_MAX_LAYERS];
+  const float* d_Wc[NRHIP_GRU4REC_MAX_LAYERS];
+  const float* d_bc[NRHIP_GRU4REC_MAX_LAYERS];
+  int width[NRHIP_GRU4REC_MAX_LAYERS];
+  int n_layers, hidden_act;
+} nrhip_gru4rec_weights;
+typedef struct nrhip_gru4rec_step_args {
+  const float* d_Ein;
+  const float* d_Q;
+  const float* d_b;
+  nrhip_gru4rec_weights w;
+  float* d_G_Ein;
+  float* d_G_Q;
+  float* d_G_b;
+  float* d_G_Wg[NRHIP_GRU4REC_MAX_LAYERS];
+  float* d_G_bg[NRHIP_GRU4REC_MAX_LAYERS];
+  float* d_G_Wc[NRHIP_GRU4REC_MAX_LAYERS];
+  float* d_G_bc[NRHIP_GRU4REC_MAX_LAYERS];
+  const float* d_state[NRHIP_GRU4REC_MAX_LAYERS];
+  float* d_h_new[NRHIP_GRU4REC_MAX_LAYERS];
+  const int32_t* d_X;
+  const int32_t* d_Y;
+  uint64_t* d_keys;
+  float* d_ws;
+  float* d_loss2;
+  int n_items, batch, final_act, loss_kind;
+  float reg;
+} nrhip_gru4rec_step_args;
+int nrhip_gru4rec_workspace_floats(int n_layers, const int* widths, int max_batch, size_t* floats);
+int nrhip_gru4rec_step(const nrhip_gru4rec_step_args* args, void* stream);
+/* Replaces `state = final_state` and `state[i][mask] = 0` of the session-parallel loop (GRU4Rec.py:160, 172-174) in
+ * one launch: d_state[l][t] = d_reset[t] ? 0 : d_h_new[l][t] for every layer and slot (the hand-over first, then the
+ * mask).  d_reset uint8 [batch], may be NULL (no slot ends). */
+int nrhip_gru4rec_advance(float* const* d_state_host, const float* const* d_h_new_host, const int* widths,
+                          int n_layers, int batch, const uint8_t* d_reset, void* stream);
+/* Replaces GRU4Rec._get_user_embeddings (GRU4Rec.py:179-225), one `sess.run([self.u_emb, self.final_state])` per time
+ * position on the host there: d_H[d_out_row ? d_out_row[k] : k] [n_last] (rows ldh apart) = the top layer's output
+ * after user d_users[k]'s items d_seq[d_seq_ptr[u] .. d_seq_ptr[u + 1]) went through the stack from a zero state; a
+ * user without items (or outside [0, n_users)) gets zeros.  One workgroup per NRHIP_GRU4REC_TILE consecutive entries
+ * of d_users loops over the time positions up to the tile's longest sequence; the states stay in LDS, a user past its
+ * end keeps its state.  Sort d_users by descending length for balance; a user's row does not depend on the tile it is
+ * in: every output is one k-ascending chain over [x, s] (then [x, r * s]) whatever the tile holds.  An item outside
+ * [0, n_items) feeds a zero input row. */
+int nrhip_gru4rec_user_states(const int64_t* d_seq_ptr, const int32_t* d_seq, int n_users, int n_items,
+                              const int32_t* d_users, const int32_t* d_out_row, int n_listed, const float* d_Ein,
+                              const nrhip_gru4rec_weights* w, float* d_H, int64_t ldh, void* stream);
+/* Replaces predict() (GRU4Rec.py:232-250): d_out[r][j] = final_act(d_H[r] . d_Q[j] + d_b[j]) for the rows d_H [n][ldh],
+ * d_out [n][ld] (ld >= n_items; the columns beyond are left alone); the dot product is the k-ascending fmaf chain. */
+int nrhip_gru4rec_scores(const float* d_H, int64_t ldh, const float* d_Q, const float* d_b, int n, int n_items, int d,
+                         int final_act, float* d_out, int64_t ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

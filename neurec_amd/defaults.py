@@ -53,6 +53,8 @@ MODELS = {
     "TransRec": [("epochs", "500"), ("batch_size", "1024"), ("embedding_size", "50"), ("reg_mf", "0.0"),
                  ("learning_rate", "0.001"), ("learner", "adam"), ("is_pairwise", "True"), ("num_neg", "4"),
                  ("loss_function", "bpr"), ("init_method", "tnormal"), ("stddev", "0.01"), ("verbose", "1")],
+    "GRU4Rec": [("lr", "0.0001"), ("reg", "0.0"), ("layers", "[100]"), ("batch_size", "256"), ("loss", "top1"),
+                ("hidden_act", "tanh"), ("final_act", "linear"), ("epochs", "1000")],
 }
 
 
