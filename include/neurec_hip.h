@@ -467,6 +467,9 @@ int nrhip_spmm_blocked_plan_destroy(void* plan);
 int nrhip_spmm_blocked_plan_info(const void* plan, int* n_workgroups, int* n_phases,
                                  int64_t* n_entries, int64_t* n_split);
 int nrhip_spmm_blocked_tune(int gathers_in_flight);
+/* How the column-masked hop of a training step stores its output Y, process-wide, for tests and A/B runs: -1 the
+ * built-in default, 0 plain, 1 nontemporal, 2 written through (the same bytes either way). */
+int nrhip_spmm_blocked_tune_store(int masked_store);
 /* The plan OWNS a copy of the matrix's (column, value) pairs in its own row order (a workgroup's pairs are one
  * contiguous slice): nrhip_spmm_blocked_pack fills it from the CSR arrays — once per matrix, again whenever the
  * values change (NGCF's node dropout rewrites them every step); a product call that hands in arrays that were not

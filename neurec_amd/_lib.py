@@ -366,6 +366,7 @@ SIGNATURES = {
     "nrhip_spmm_blocked_plan_destroy": [p],
     "nrhip_spmm_blocked_plan_info": [p, p, p, p, p],
     "nrhip_spmm_blocked_tune": [i32],
+    "nrhip_spmm_blocked_tune_store": [i32],
     "nrhip_spmm_blocked": [p, p, p, p, p, p, p, p, p, p, p],
     "nrhip_spmm_plan_attach_blocked": [p, p, i32],
     "nrhip_spmm_plan_has_blocked": [p, i32],

@@ -61,6 +61,29 @@ struct BlockedPlan : nr_plan::PlanArrays<int4> {
 };
 
 
+// Store policy of a hop's row output Y (compile time).  A plain store leaves the line dirty in the XCD's L2 until
+// the kernel boundary writes it back, and the next launch waits for that; the other two let it leave while the
+// kernel still runs: nontemporal, or written through (sc1) with a raw buffer store (y_bytes: the size of Y, the
+// descriptor's range; offsets are 32 bits).  Same bytes.  Measured: profiles/r18_latency_chain.txt.
+enum { kStorePlain = 0, kStoreNt = 1, kStoreWt = 2 };
+typedef float nr_f32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int nr_u32x4 __attribute__((ext_vector_type(4)));
+
+template <int ST>
+__device__ __forceinline__ void row_store(float4* __restrict__ Y, uint32_t y_bytes, int64_t o, float4 y) {
+  if constexpr (ST == kStoreNt) {
+    __builtin_nontemporal_store(nr_f32x4{y.x, y.y, y.z, y.w}, (nr_f32x4*)(Y + o));
+  } else if constexpr (ST == kStoreWt) {
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)Y, 0, (int)y_bytes, 0x00020000);
+    __builtin_amdgcn_raw_buffer_store_b128(nr_u32x4{__float_as_uint(y.x), __float_as_uint(y.y), __float_as_uint(y.z),
+                                                    __float_as_uint(y.w)},
+                                           rs, (int)(uint32_t)(o * 16), 0, 16);
+  } else {
+    Y[o] = y;
+  }
+}
+
+
 // Optional fused optimiser epilogue (last backward hop of a LightGCN step): instead of storing
 // y, treat g = y + grad_b[row] as the dense gradient of `var` and apply TF-1.12 ApplyAdam to the
 // row (training_ops: m += (g-m)(1-b1); v += (g²-v)(1-b2); var -= m·alpha/(sqrt(v)+eps)).
@@ -120,7 +143,15 @@ __device__ __forceinline__ void blocked_epilogue(const float4* s_acc, int r0, in
       ad.var[o] = w; ad.m[o] = mm; ad.v[o] = vv;
       continue;
     }
-    if (Y) Y[o] = y;
+    if (Y) {
+      // the d = 64 full passes write Y through: its 18 MB do not wait dirty in the L2s for the kernel boundary
+      if constexpr (LPR == 16 && !MASKED) {
+        if ((uint64_t)o * 16 + 16 <= 0xFFFFFFFFull) row_store<kStoreWt>(Y, 0xFFFFFFFFu, o, y);
+        else Y[o] = y;
+      } else {
+        Y[o] = y;
+      }
+    }
     if (sum_out) {
       const float4 si = sum_in[o];
       sum_out[o] = make_float4(__fadd_rn(si.x, y.x), __fadd_rn(si.y, y.y), __fadd_rn(si.z, y.z),
@@ -349,17 +380,18 @@ __device__ __forceinline__ float4 chain_sum(float4 si, const LayerChain& ch, int
   return si;
 }
 
+template <int ST = kStorePlain>
 __device__ __forceinline__ void masked_row_out(float4 y, int64_t o, const float4* __restrict__ addend,
                                                bool addend_row_nonzero, float4* __restrict__ Y,
                                                const float4* sum_in, float4* sum_out,
-                                               const LayerChain* chain = nullptr) {
+                                               const LayerChain* chain = nullptr, uint32_t y_bytes = 0) {
   if (addend) {
     float4 av = make_float4(0.f, 0.f, 0.f, 0.f);       // a row promised zero is not read
     if (addend_row_nonzero) av = addend[o];
     y.x = __fadd_rn(y.x, av.x); y.y = __fadd_rn(y.y, av.y);
     y.z = __fadd_rn(y.z, av.z); y.w = __fadd_rn(y.w, av.w);
   }
-  if (Y) Y[o] = y;
+  if (Y) row_store<ST>(Y, y_bytes, o, y);
   if (sum_out) {
     float4 si = sum_in[o];
     if (chain) si = chain_sum(si, *chain, o);
@@ -378,11 +410,14 @@ __device__ __forceinline__ void masked_row_out(float4 y, int64_t o, const float4
 // (vmcnt(0)), which silently turns the ring into one round in flight (measured: 14 us -> see
 // profiles/r01_exp_masked_hops.txt).  The "+ 1" is the epilogue operand of the row a round
 // completes (addend, else sum_in), requested with the round's gathers for the same reason.
+// ST: store policy of Y (row_store; only the column-masked backward hop asks for another than plain).
+template <int ST = kStorePlain>
 __device__ __forceinline__ void staged_walk(const int4* s_ent, const int2* s_iv, int ne, int r0,
                                             const float4* __restrict__ X, float4* __restrict__ Y,
                                             const float4* __restrict__ addend, const float4* sum_in,
                                             float4* sum_out, float4* s_part, int kRMax, int wave,
-                                            int g, int c, LayerChain chain = LayerChain{nullptr, nullptr}) {
+                                            int g, int c, LayerChain chain = LayerChain{nullptr, nullptr},
+                                            uint32_t y_bytes = 0) {
   constexpr int RS = 16, LPR = 16, GPW = 4, kGroups = 64;
   constexpr int kQ = 4;
   struct Round { float4 x[kQ]; float4 pre; int off, n, slot, owner; bool first, last, live, valid; };
@@ -449,7 +484,7 @@ __device__ __forceinline__ void staged_walk(const int4* s_ent, const int2* s_iv,
           y.x = __fadd_rn(y.x, av.x); y.y = __fadd_rn(y.y, av.y);
           y.z = __fadd_rn(y.z, av.z); y.w = __fadd_rn(y.w, av.w);
         }
-        if (Y) Y[o] = y;
+        if (Y) row_store<ST>(Y, y_bytes, o, y);
         if (sum_out) {
           float4 si = r.pre;
           if (addend) si = sum_in[o];                      // both operands: this one is read late
@@ -479,7 +514,7 @@ __device__ __forceinline__ void staged_walk(const int4* s_ent, const int2* s_iv,
   }
 }
 
-template <bool COLMASK, bool ROWMASK>
+template <bool COLMASK, bool ROWMASK, int ST = kStorePlain>
 __global__ __launch_bounds__(16 * NR_WAVE) void spmm_staged_masked_kernel(
     const int32_t* __restrict__ wg_row0, const int32_t* __restrict__ wg_ent_off,
     const int32_t* __restrict__ wg_cmb_off, const uint32_t* __restrict__ wg_nnz,
@@ -487,7 +522,7 @@ __global__ __launch_bounds__(16 * NR_WAVE) void spmm_staged_masked_kernel(
     const int32_t* __restrict__ indices, const float* __restrict__ vals,
     const float4* __restrict__ X, float4* __restrict__ Y, const float4* __restrict__ addend,
     const float4* sum_in, float4* sum_out, const uint8_t* __restrict__ col_mask,
-    const uint8_t* __restrict__ row_mask, int addend_masked, int kRMax, int p_max, int ent_cap) {
+    const uint8_t* __restrict__ row_mask, int addend_masked, int kRMax, int p_max, int ent_cap, uint32_t y_bytes) {
   constexpr int RS = 16, LPR = 16, GPW = 4, kGroups = 64;
   extern __shared__ float4 s_mem[];
   float4* s_part = s_mem;                                          // [p_max][16]
@@ -572,7 +607,8 @@ __global__ __launch_bounds__(16 * NR_WAVE) void spmm_staged_masked_kernel(
     }
     if (ei < ne && c == 0) s_ent[ei].y = w;
   }
-  staged_walk(s_ent, s_iv, ne, 0, X, Y, addend, sum_in, sum_out, s_part, kRMax, wave, g, c);
+  staged_walk<ST>(s_ent, s_iv, ne, 0, X, Y, addend, sum_in, sum_out, s_part, kRMax, wave, g, c,
+                  LayerChain{nullptr, nullptr}, y_bytes);
   if (c1 > c0) {                                           // workgroup-uniform
     __syncthreads();
     for (int ci = c0 + wave * GPW + g; ci < c1; ci += kGroups) {
@@ -588,7 +624,7 @@ __global__ __launch_bounds__(16 * NR_WAVE) void spmm_staged_masked_kernel(
       }
       bool addend_on = true;
       if constexpr (COLMASK) addend_on = !addend_masked || col_mask[cm.w] != 0;
-      masked_row_out(acc, (int64_t)cm.w * RS + c, addend, addend_on, Y, sum_in, sum_out);
+      masked_row_out<ST>(acc, (int64_t)cm.w * RS + c, addend, addend_on, Y, sum_in, sum_out, nullptr, y_bytes);
     }
   }
 }
@@ -1178,6 +1214,8 @@ int launch_wanted_wave(const BlockedPlan* p, const int32_t* d_indices, const flo
 }
 
 int s_gathers_in_flight = 8;     // tuning knob (nrhip_spmm_blocked_tune)
+constexpr int kMaskedStoreDefault = kStoreWt;
+int s_masked_store = kMaskedStoreDefault;   // tuning knob (nrhip_spmm_blocked_tune_store): how the column-masked hop stores Y
 
 // (column, value) pairs copied into the plan's row order: row k of the order is CSR positions
 // [src[k], src[k] + dst[k+1] - dst[k]) -> packed positions [dst[k], dst[k+1]).  Once per matrix.
@@ -1218,6 +1256,8 @@ static hipError_t allow_plan_lds(const BlockedPlan* p) {
   if (p->ww_ok) allow((const void*)spmm_wanted_wave_kernel, ww_lds_bytes(p));
   if (p->colmask_ok)
     for (const void* fn : {(const void*)spmm_staged_masked_kernel<true, false>,
+                           (const void*)spmm_staged_masked_kernel<true, false, kStoreNt>,
+                           (const void*)spmm_staged_masked_kernel<true, false, kStoreWt>,
                            (const void*)spmm_staged_masked_kernel<false, true>,
                            (const void*)spmm_staged_masked_kernel<true, true>})
       allow(fn, colmask_lds_bytes(p));
@@ -1350,6 +1390,14 @@ int nrhip_spmm_blocked_tune(int gathers_in_flight) {
   return NR_OK;
 }
 
+int nrhip_spmm_blocked_tune_store(int masked_store) {
+  NR_REQUIRE(masked_store >= -1 && masked_store <= kStoreWt, NR_ERR_ARG,
+             "spmm_blocked_tune_store: store policy %d (-1 the default, 0 plain, 1 nontemporal, 2 written through)",
+             masked_store);
+  s_masked_store = masked_store < 0 ? kMaskedStoreDefault : masked_store;
+  return NR_OK;
+}
+
 int nrhip_spmm_blocked_plan_destroy(void* plan) {
   delete (BlockedPlan*)plan;
   return NR_OK;
@@ -1396,15 +1444,20 @@ int nrhip_spmm_blocked(const void* plan, const int32_t* d_indices, const float* 
   if (p->colmask_ok && masked) {
     // an addend that is the operand itself shares its promise (zero rows where the mask is 0)
     const int addend_masked = d_x_row_nonzero && d_addend == d_X ? 1 : 0;
-#define NR_STAGED(CM, RM)                                                                          \
-  hipLaunchKernelGGL((spmm_staged_masked_kernel<CM, RM>), grid, block, colmask_lds_bytes(p), st,   \
+    // Y's bytes for the written-through form's buffer descriptor (32-bit offsets: a larger Y is stored plainly)
+    const uint64_t y_all = (uint64_t)p->n_rows * p->d * 4;
+    const int store = d_Y && y_all <= 0xFFFFFFFFull ? s_masked_store : kStorePlain;
+#define NR_STAGED(CM, RM, ST)                                                                      \
+  hipLaunchKernelGGL((spmm_staged_masked_kernel<CM, RM, ST>), grid, block, colmask_lds_bytes(p), st, \
                      p->wg_row0, p->wg_ent_off, p->wg_cmb_off, p->wg_nnz, p->ent, p->cmb, p->pk_idx, \
                      p->pk_val, (const float4*)d_X, (float4*)d_Y, (const float4*)d_addend,          \
                      (const float4*)d_sum_in, (float4*)d_sum_out, d_x_row_nonzero, d_y_row_wanted,  \
-                     addend_masked, p->r_max, p->p_max, p->ent_cap)
-    if (d_x_row_nonzero && d_y_row_wanted) NR_STAGED(true, true);
-    else if (d_x_row_nonzero) NR_STAGED(true, false);
-    else NR_STAGED(false, true);
+                     addend_masked, p->r_max, p->p_max, p->ent_cap, (uint32_t)y_all)
+    if (d_x_row_nonzero && d_y_row_wanted) NR_STAGED(true, true, kStorePlain);
+    else if (d_x_row_nonzero && store == kStoreNt) NR_STAGED(true, false, kStoreNt);
+    else if (d_x_row_nonzero && store == kStoreWt) NR_STAGED(true, false, kStoreWt);
+    else if (d_x_row_nonzero) NR_STAGED(true, false, kStorePlain);
+    else NR_STAGED(false, true, kStorePlain);
 #undef NR_STAGED
     NR_LAUNCH_CHECK();
     return NR_OK;
