@@ -768,8 +768,12 @@ int nrhip_ngcf_layer_bwd(const float* d_ego, const float* d_S, const float* d_Wg
  *   nrhip_vae_decoder_loss_grad   d_S holds g1·W_p1ᵀ (bias NOT added) on entry (contents on exit
  *                      unspecified); writes nll[b] = -Σ_i log_softmax·x, dW_p1 ([n_items][h]),
  *                      db_p1, dg1 — both products on the fp32 matrix cores, dLoss/dlogits formed in
- *                      registers from the logits (never stored).
+ *                      registers from the logits (never stored).  The slab's rows and the bias are
+ *                      read 16 bytes at a time: d_S and d_bp1 16-byte aligned, ld a multiple of 4
+ *                      (nrhip_score_gemm's buffers are), else NRHIP_ERR_ARG.
  *   nrhip_vae_mid_backward        the 16/32-wide layers' backward and weight gradients.
+ *   batch == 0: every entry point of this block (nrhip_vae_step included) launches nothing, writes nothing
+ *                      and returns NRHIP_OK.
  *   nrhip_vae_dwq0     scatter of h0ᵀ·da1 into a zeroed dense [n_items][h] gradient.
  * act: 0 tanh, 1 sigmoid, 2 relu, 3 identity (util/tool.py activation_function). */
 int nrhip_vae_encode(const int64_t* d_indptr, const int32_t* d_indices, const int32_t* d_rows,

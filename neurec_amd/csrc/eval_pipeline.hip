@@ -168,7 +168,8 @@ int nrhip_eval_pruned(const NrhipEvalPruned* a, void* stream) {
 // ---------------------------------------------------------------------------------------------------------------
 extern "C" int nrhip_vae_step(const NrhipVaeStep* a, const int32_t* d_rows, int batch, float anneal, float keep,
                               float adam_alpha, uint64_t step, int want_loss, int apply, void* stream) {
-  NR_REQUIRE(a && d_rows && batch >= 1, NR_ERR_ARG, "vae_step: bad arguments");
+  NR_REQUIRE(a && batch >= 0 && (batch == 0 || d_rows), NR_ERR_ARG, "vae_step: bad arguments");
+  if (batch == 0) return NR_OK;                      // no rows: no gradient, no loss statistics, no Adam step
   float* const* P = a->P;
   float* const* G = a->G;
   // order of the eight variables: Wq0, bq0, Wq1, bq1, Wp0, bp0, Wp1t, bp1

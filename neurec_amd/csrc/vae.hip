@@ -673,17 +673,28 @@ int nrhip_vae_workspace_bytes(int batch, int cols, size_t* bytes) {
   return NR_OK;
 }
 
-/* d_S holds g1·W_p1ᵀ (no bias) on entry and is only read. */
+/* d_S holds g1·W_p1ᵀ (no bias) on entry and is only read.
+   Alignment contract: vae_softmax_stats_kernel reads every row of the slab and the bias 16 bytes at a time (float4
+   at d_S + r·ld and at d_bp1), so d_S and d_bp1 must be 16-byte aligned and ld a multiple of 4 floats; the columns
+   [cols, ld) are never read.  The slab's only producer, ScoreGemm.new_score_buffer, pads ld to 64 floats in a fresh
+   allocation and the bias is a variable of its own: both hold.  Anything else (a column block of a wider buffer,
+   a bias sliced at an odd offset) is refused here, before any launch.  batch == 0 is accepted and touches nothing. */
 int nrhip_vae_decoder_loss_grad(float* d_S, int64_t ld, int batch, int cols, int h,
                                 const float* d_bp1, const int64_t* d_indptr,
                                 const int32_t* d_indices, const int32_t* d_rows,
                                 const float* d_G1, const float* d_Wp1, float* d_nll,
                                 float* d_dWp1, float* d_dbp1, float* d_dG1, void* d_ws,
                                 size_t ws_bytes, void* stream) {
-  NR_REQUIRE(d_S && d_bp1 && d_indptr && d_indices && d_rows && d_G1 && d_Wp1 && d_nll && d_dWp1 &&
-                 d_dbp1 && d_dG1 && d_ws && ld >= cols && batch >= 1 && cols >= 1,
+  // (an empty tensor has no storage: the per-row pointers are required only when there are rows)
+  NR_REQUIRE(ld >= cols && batch >= 0 && cols >= 1 &&
+                 (batch == 0 || (d_S && d_bp1 && d_indptr && d_indices && d_rows && d_G1 && d_Wp1 && d_nll && d_dWp1 &&
+                                 d_dbp1 && d_dG1 && d_ws)),
              NR_ERR_ARG, "vae_decoder_loss_grad: bad arguments");
   NR_REQUIRE(h >= 1 && h <= kMaxD, NR_ERR_UNSUPPORTED, "vae_decoder: hidden %d > 32", h);
+  if (batch == 0) return NR_OK;
+  NR_REQUIRE(ld % 4 == 0 && ((uintptr_t)d_S & 15) == 0 && ((uintptr_t)d_bp1 & 15) == 0, NR_ERR_ARG,
+             "vae_decoder_loss_grad: the slab and the bias are read as float4 (16-byte aligned pointers, ld %% 4 == 0); "
+             "got ld %lld", (long long)ld);
   const int words = (cols + 31) / 32;
   const size_t bits_bytes = nr_align_up((size_t)batch * words * sizeof(uint32_t), 256);
   float* part = (float*)((char*)d_ws + bits_bytes);
@@ -722,12 +733,14 @@ int nrhip_vae_mid_backward(int batch, int h, int z, int act, float anneal, const
                            const float* d_Wp0, const float* d_Wq1, float* d_DA3, float* d_DH2,
                            float* d_DA1, float* d_dWp0, float* d_dbp0, float* d_dWq1,
                            float* d_dbq1, float* d_dbq0, void* stream) {
-  NR_REQUIRE(d_dG1 && d_G1 && d_H1 && d_MU && d_LOGVAR && d_EPSSTD && d_ZS && d_Wp0 && d_Wq1 &&
-                 d_DA3 && d_DH2 && d_DA1 && d_dWp0 && d_dbp0 && d_dWq1 && d_dbq1 && d_dbq0 &&
-                 batch >= 1,
+  NR_REQUIRE(batch >= 0 && (batch == 0 || (d_dG1 && d_G1 && d_H1 && d_MU && d_LOGVAR && d_EPSSTD && d_ZS && d_Wp0 &&
+                                           d_Wq1 && d_DA3 && d_DH2 && d_DA1 && d_dWp0 && d_dbp0 && d_dWq1 && d_dbq1 &&
+                                           d_dbq0)),
              NR_ERR_ARG, "vae_mid_backward: bad arguments");
   NR_REQUIRE(h >= 1 && h <= kMaxD && z >= 1 && 2 * z <= kMaxD, NR_ERR_UNSUPPORTED,
              "vae_mid_backward: widths outside the built range");
+  NR_REQUIRE(act >= 0 && act <= 3, NR_ERR_ARG, "vae_mid_backward: bad activation %d", act);
+  if (batch == 0) return NR_OK;                              // no rows: the gradients are left as they are
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(vae_mid_bwd_kernel, dim3((batch + 3) / 4), dim3(256), 0, st, batch, h, z, act,
                      anneal, 1.0f / (float)batch, d_dG1, d_G1, d_H1, d_MU, d_LOGVAR, d_EPSSTD,

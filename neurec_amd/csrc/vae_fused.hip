@@ -65,7 +65,12 @@ __device__ __forceinline__ float exp_nonpos(float x) {
 
 // e^(x - ref) = 2^(x·log2e - ref·log2e): v_exp_f32 on one fma (both passes).  Pass 1's Σ exp:  The single rounding of the
 // exponent costs a term a relative error of 6e-8·|x - ref|·log2e — weighted by the term itself, |t|·e^t <= 1/e, so
-// the SUM (>= 1: the maximum's own term) keeps a relative error under 1e-7 and lse an absolute one under 1e-7; the
+// the SUM (>= 1: the maximum's own term) keeps a relative error under 1e-7 from that rounding.  The other operand is
+// rounded too: ref·log2e (pass 1's nref, pass 2's nlse) is a float32 product, off by up to 2^-24·|ref|·log2e, the same
+// for every term folded against that ref — a factor 2^δ on their sum, so lse carries an absolute error of up to
+// 1e-7 + 6e-8·|ref|: about half an ulp of a number of the maximum logit's size, the size of lse itself (an earlier
+// version of this comment claimed 1e-7 outright, which holds only for |ref| of order 1; tests/test_vae_gpu.py runs
+// logits spanning 130 per row, lse near 80, and holds both decoders to the same bound).  The
 // full-precision form above costs 11 instructions per logit against 2, and MFMA and VALU time add up here.
 __device__ __forceinline__ float exp2_scaled(float x_log2e_minus_ref) {
   return __builtin_amdgcn_exp2f(x_log2e_minus_ref);
@@ -606,7 +611,7 @@ int launch_grad(const FusedArgs& a, int n_wg, hipStream_t st) {
 extern "C" {
 
 int nrhip_vae_decoder_fused_workspace_bytes(int batch, int cols, size_t* bytes) {
-  NR_REQUIRE(bytes && batch >= 1 && cols >= 1, NR_ERR_ARG, "vae_decoder_fused_workspace_bytes: bad arguments");
+  NR_REQUIRE(bytes && batch >= 0 && cols >= 1, NR_ERR_ARG, "vae_decoder_fused_workspace_bytes: bad arguments");
   *bytes = fused_layout(batch, cols).total;
   return NR_OK;
 }
@@ -615,10 +620,13 @@ int nrhip_vae_decoder_fused(int batch, int cols, int h, const float* d_G1, const
                             const float* d_bp1, const int64_t* d_indptr, const int32_t* d_indices,
                             const int32_t* d_rows, float* d_nll, float* d_dWp1, float* d_dbp1,
                             float* d_dG1, void* d_ws, size_t ws_bytes, float* d_dbg_logits, void* stream) {
-  NR_REQUIRE(d_G1 && d_Wp1 && d_bp1 && d_indptr && d_indices && d_rows && d_nll && d_dWp1 && d_dbp1 && d_dG1 &&
-                 d_ws && batch >= 1 && cols >= 1,
+  // (an empty tensor has no storage: the per-row pointers are required only when there are rows)
+  NR_REQUIRE(batch >= 0 && cols >= 1 &&
+                 (batch == 0 || (d_G1 && d_Wp1 && d_bp1 && d_indptr && d_indices && d_rows && d_nll && d_dWp1 &&
+                                 d_dbp1 && d_dG1 && d_ws)),
              NR_ERR_ARG, "vae_decoder_fused: bad arguments");
   NR_REQUIRE(h >= 1 && h <= kT, NR_ERR_UNSUPPORTED, "vae_decoder_fused: hidden %d > 32", h);
+  if (batch == 0) return NR_OK;                      // no rows: nothing is launched, the gradients are left as they are
   const FusedLayout L = fused_layout(batch, cols);
   NR_REQUIRE(ws_bytes >= L.total, NR_ERR_WORKSPACE,
              "vae_decoder_fused: workspace too small (nrhip_vae_decoder_fused_workspace_bytes)");
