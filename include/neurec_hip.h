@@ -481,6 +481,20 @@ int nrhip_spmm_blocked(const void* plan, const int32_t* d_indices, const float* 
                        const float* d_X, float* d_Y, const float* d_addend, const float* d_sum_in,
                        float* d_sum_out, const uint8_t* d_x_row_nonzero,
                        const uint8_t* d_y_row_wanted, void* stream);
+/* The unmasked product with a promise about a row-sparse addend: d_addend_row_flag[r] == 0 says row r of d_addend is
+ * all zero, and the lane-group pass does not read it (the inner backward hops of a LightGCN step: H is non-zero on
+ * the batch rows only, whose flags the batch-rows hop set).  NULL flags: nrhip_spmm_blocked / nrhip_spmm_csr.
+ * Flags need an addend and no masks.  nrhip_spmm_csr_flagged: behind the matrix handle; a width without a lane-group
+ * schedule reads the addend densely (same result).  _tune_addend_flag(0): ignore the flags process-wide (A/B runs). */
+int nrhip_spmm_blocked_flagged(const void* plan, const int32_t* d_indices, const float* d_vals,
+                               const float* d_X, float* d_Y, const float* d_addend,
+                               const uint8_t* d_addend_row_flag, const float* d_sum_in, float* d_sum_out,
+                               const uint8_t* d_x_row_nonzero, const uint8_t* d_y_row_wanted, void* stream);
+int nrhip_spmm_csr_flagged(const void* plan, const int64_t* d_indptr, const int32_t* d_indices,
+                           const float* d_vals, const float* d_X, int d, float* d_Y,
+                           const float* d_addend, const uint8_t* d_addend_row_flag, const float* d_sum_in,
+                           float* d_sum_out, void* d_ws, size_t ws_bytes, void* stream);
+int nrhip_spmm_blocked_tune_addend_flag(int on);
 int nrhip_spmm_plan_attach_blocked(void* plan, const void* blocked_plan, int d);
 
 /* Last backward hop of a step and the optimiser in one pass (LightGCN.py:130,140 fused):

@@ -368,6 +368,9 @@ SIGNATURES = {
     "nrhip_spmm_blocked_tune": [i32],
     "nrhip_spmm_blocked_tune_store": [i32],
     "nrhip_spmm_blocked": [p, p, p, p, p, p, p, p, p, p, p],
+    "nrhip_spmm_blocked_flagged": [p, p, p, p, p, p, p, p, p, p, p, p],
+    "nrhip_spmm_csr_flagged": [p, p, p, p, p, i32, p, p, p, p, p, p, sz, p],
+    "nrhip_spmm_blocked_tune_addend_flag": [i32],
     "nrhip_spmm_plan_attach_blocked": [p, p, i32],
     "nrhip_spmm_plan_has_blocked": [p, i32],
     "nrhip_spmm_plan_has_wanted": [p, i32],

@@ -46,6 +46,11 @@ extern "C" int nrhip_spmm_blocked(const void* plan, const int32_t* d_indices, co
                                   const float* d_sum_in, float* d_sum_out,
                                   const uint8_t* d_x_row_nonzero, const uint8_t* d_y_row_wanted,
                                   void* stream);
+extern "C" int nrhip_spmm_blocked_flagged(const void* plan, const int32_t* d_indices, const float* d_vals,
+                                          const float* d_X, float* d_Y, const float* d_addend,
+                                          const uint8_t* d_addend_row_flag, const float* d_sum_in,
+                                          float* d_sum_out, const uint8_t* d_x_row_nonzero,
+                                          const uint8_t* d_y_row_wanted, void* stream);
 
 extern "C" int nrhip_spmm_blocked_wanted_layers(const void* plan, const int32_t* d_indices,
                                                 const float* d_vals, const float* d_X,
@@ -1014,7 +1019,8 @@ static int spmm_dispatch(const char* who, const void* plan, const int64_t* d_ind
                          const int32_t* d_indices, const float* d_vals, const float* d_X, int d,
                          float* d_Y, const float* d_addend, const float* d_sum_in,
                          float* d_sum_out, const uint8_t* d_col_mask, const uint8_t* d_row_mask,
-                         void* d_ws, size_t ws_bytes, void* stream) {
+                         void* d_ws, size_t ws_bytes, void* stream,
+                         const uint8_t* d_addend_row_flag = nullptr) {
   NR_REQUIRE(plan && d_indptr && d_indices && d_vals && d_X && (d_Y || d_sum_out), NR_ERR_ARG,
              "%s: null pointer argument", who);
   NR_REQUIRE((d_sum_out == nullptr) || (d_sum_in != nullptr), NR_ERR_ARG,
@@ -1023,8 +1029,8 @@ static int spmm_dispatch(const char* who, const void* plan, const int64_t* d_ind
   hipStream_t st = (hipStream_t)stream;
   const int bslot = blocked_slot(d);
   if (bslot >= 0 && p->blocked[bslot])   // persistent lane-group kernel (same contract, same masks)
-    return nrhip_spmm_blocked(p->blocked[bslot], d_indices, d_vals, d_X, d_Y, d_addend, d_sum_in,
-                              d_sum_out, d_col_mask, d_row_mask, stream);
+    return nrhip_spmm_blocked_flagged(p->blocked[bslot], d_indices, d_vals, d_X, d_Y, d_addend, d_addend_row_flag,
+                                      d_sum_in, d_sum_out, d_col_mask, d_row_mask, stream);
   if (d < 64)   // the 16/32-wide path has no work-skipping variants
     NR_REQUIRE(d_row_mask == nullptr, NR_ERR_UNSUPPORTED,
                "%s: row mask needs an embedding dim >= 64", who);
@@ -1052,6 +1058,17 @@ int nrhip_spmm_csr(const void* plan, const int64_t* d_indptr, const int32_t* d_i
                    size_t ws_bytes, void* stream) {
   return spmm_dispatch("spmm_csr", plan, d_indptr, d_indices, d_vals, d_X, d, d_Y, d_addend,
                        d_sum_in, d_sum_out, nullptr, nullptr, d_ws, ws_bytes, stream);
+}
+
+/* nrhip_spmm_csr with a promise about a row-sparse addend (rows whose flag is 0 are all zero): the lane-group pass
+ * does not read those rows; the other kernels read the addend densely, which gives the same result. */
+int nrhip_spmm_csr_flagged(const void* plan, const int64_t* d_indptr, const int32_t* d_indices,
+                           const float* d_vals, const float* d_X, int d, float* d_Y,
+                           const float* d_addend, const uint8_t* d_addend_row_flag, const float* d_sum_in,
+                           float* d_sum_out, void* d_ws, size_t ws_bytes, void* stream) {
+  NR_REQUIRE(!d_addend_row_flag || d_addend, NR_ERR_ARG, "spmm_csr_flagged: addend row flags without an addend");
+  return spmm_dispatch("spmm_csr_flagged", plan, d_indptr, d_indices, d_vals, d_X, d, d_Y, d_addend,
+                       d_sum_in, d_sum_out, nullptr, nullptr, d_ws, ws_bytes, stream, d_addend_row_flag);
 }
 
 int nrhip_spmm_csr_masked(const void* plan, const int64_t* d_indptr, const int32_t* d_indices,

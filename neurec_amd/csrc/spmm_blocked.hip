@@ -96,6 +96,10 @@ struct AdamEpilogue {
 };
 
 
+// An entry of the workgroup's staged row list: the row, and in the sign bit "this row's flag is 0" (rows are < 2^31).
+constexpr int kRowBits = 0x7FFFFFFF;
+constexpr int kRowUnflagged = (int)0x80000000u;
+
 // Epilogue shared by the full-pass kernels: the workgroup's finished row sums sit in LDS
 // (s_acc[slot][LPR]); y += addend, then either the ApplyAdam epilogue or the stores of y and of the
 // running layer sum — a row is LPR lanes x 16 B (whole cache lines at d >= 32), so a row LIST
@@ -108,18 +112,17 @@ __device__ __forceinline__ void blocked_epilogue(const float4* s_acc, int r0, in
                                                  const int32_t* s_rows = nullptr) {
   for (int i = tid; i < nr * LPR; i += nthreads) {
     // s_rows: the workgroup's row list (LDS; dealt rows), else its rows are the run [r0, r0 + nr)
-    const int row = s_rows ? s_rows[i / LPR] : r0 + i / LPR;
+    const int rw = s_rows ? s_rows[i / LPR] : r0 + i / LPR;
+    const int row = rw & kRowBits;
     if constexpr (MASKED) {
       if (row_mask && row_mask[row] == 0) continue;
     }
     const int64_t o = (int64_t)row * LPR + (i & (LPR - 1));
     float4 y = s_acc[i];
-    // with row flags (re-arming step buffers) the addend / grad_b rows of unflagged rows are all
-    // zero by contract and are not read: two of the seven epilogue streams touch batch rows only
-    bool flagged = true;
-    if constexpr (ADAM) {
-      if (ad.flag_rw) flagged = ad.flag_rw[row] != 0;
-    }
+    // with row flags (the addend of a backward hop, the step buffers the Adam pass re-arms) the addend / grad_b rows
+    // of unflagged rows are all zero by contract and are not read: these streams touch batch rows only.  The flag
+    // was staged with the row list (kRowUnflagged), so the loads below wait for LDS, not for a flag from memory.
+    const bool flagged = rw >= 0;
     float4 hv = make_float4(0.f, 0.f, 0.f, 0.f);
     if (addend) {
       if (flagged) hv = addend[o];
@@ -183,7 +186,7 @@ __global__ __launch_bounds__(kWaves* NR_WAVE) void spmm_blocked_kernel(
     const float4* __restrict__ X, float4* __restrict__ Y, const float4* __restrict__ addend,
     const float4* sum_in, float4* sum_out, const uint8_t* __restrict__ col_mask,
     const uint8_t* __restrict__ row_mask, int kRMax, AdamEpilogue ad, const int32_t* __restrict__ row_of,
-    int kPMax) {
+    int kPMax, const uint8_t* __restrict__ addend_flag) {
   constexpr int LPR = D / 4;                   // lanes per row: 16-byte pieces of a d-float row
   constexpr int GPW = NR_WAVE / LPR;           // lane groups (rows in flight) per wave: 4 / 2 / 1
   constexpr int kGroups = kWaves * GPW;
@@ -199,7 +202,16 @@ __global__ __launch_bounds__(kWaves* NR_WAVE) void spmm_blocked_kernel(
   NR_BLK_STAMP(0);
   const int r0 = wg_row0[wg], nr = wg_nrows[wg];
   int32_t* s_rows = (int32_t*)(s_acc + (size_t)(kRMax + kPMax) * LPR);
-  for (int i = tid; i < nr; i += kWaves * NR_WAVE) s_rows[i] = row_of[r0 + i];   // read back in the epilogue
+  // the row list, read back in the epilogue, and with it the rows' flags (addend_flag: 0 = the addend row is zero
+  // and is not read; the Adam pass takes the step's own flags): one byte gather per row here, none in the epilogue
+  const uint8_t* fl = ADAM ? ad.flag_rw : addend_flag;                           // workgroup-uniform
+  // (keeping a thread's entry in registers over the walk, so that the flag's round trip runs under the walk's first
+  // loads, measured the same: profiles/r19_addend_by_flag.txt)
+  for (int i = tid; i < nr; i += kWaves * NR_WAVE) {
+    int row = row_of[r0 + i];
+    if (fl && fl[row] == 0) row |= kRowUnflagged;
+    s_rows[i] = row;
+  }
   for (int i = tid; i < nr * LPR; i += kWaves * NR_WAVE) s_acc[i] = make_float4(0.f, 0.f, 0.f, 0.f);
   __syncthreads();
   NR_BLK_STAMP(1);
@@ -1215,6 +1227,7 @@ int launch_wanted_wave(const BlockedPlan* p, const int32_t* d_indices, const flo
 
 int s_gathers_in_flight = 8;     // tuning knob (nrhip_spmm_blocked_tune)
 constexpr int kMaskedStoreDefault = kStoreWt;
+int s_addend_by_flag = 1;        // tuning knob (nrhip_spmm_blocked_tune_addend_flag): 0 reads a flagged addend densely
 int s_masked_store = kMaskedStoreDefault;   // tuning knob (nrhip_spmm_blocked_tune_store): how the column-masked hop stores Y
 
 // (column, value) pairs copied into the plan's row order: row k of the order is CSR positions
@@ -1398,6 +1411,11 @@ int nrhip_spmm_blocked_tune_store(int masked_store) {
   return NR_OK;
 }
 
+int nrhip_spmm_blocked_tune_addend_flag(int on) {
+  s_addend_by_flag = on ? 1 : 0;
+  return NR_OK;
+}
+
 int nrhip_spmm_blocked_plan_destroy(void* plan) {
   delete (BlockedPlan*)plan;
   return NR_OK;
@@ -1414,14 +1432,33 @@ int nrhip_spmm_blocked_plan_info(const void* plan, int* n_workgroups, int* n_pha
   return NR_OK;
 }
 
+int nrhip_spmm_blocked_flagged(const void* plan, const int32_t* d_indices, const float* d_vals,
+                               const float* d_X, float* d_Y, const float* d_addend,
+                               const uint8_t* d_addend_row_flag, const float* d_sum_in, float* d_sum_out,
+                               const uint8_t* d_x_row_nonzero, const uint8_t* d_y_row_wanted, void* stream);
+
 int nrhip_spmm_blocked(const void* plan, const int32_t* d_indices, const float* d_vals,
                        const float* d_X, float* d_Y, const float* d_addend, const float* d_sum_in,
                        float* d_sum_out, const uint8_t* d_x_row_nonzero,
                        const uint8_t* d_y_row_wanted, void* stream) {
+  return nrhip_spmm_blocked_flagged(plan, d_indices, d_vals, d_X, d_Y, d_addend, nullptr, d_sum_in, d_sum_out,
+                                    d_x_row_nonzero, d_y_row_wanted, stream);
+}
+
+/* nrhip_spmm_blocked with a promise about the addend: d_addend_row_flag[r] == 0 says row r of d_addend is all zero,
+ * and the unmasked pass then does not read it (NULL: no promise).  The masked forms have their own promise
+ * (an addend that is the operand) and take no flags. */
+int nrhip_spmm_blocked_flagged(const void* plan, const int32_t* d_indices, const float* d_vals,
+                               const float* d_X, float* d_Y, const float* d_addend,
+                               const uint8_t* d_addend_row_flag, const float* d_sum_in, float* d_sum_out,
+                               const uint8_t* d_x_row_nonzero, const uint8_t* d_y_row_wanted, void* stream) {
   NR_REQUIRE(plan && d_indices && d_vals && d_X && (d_Y || d_sum_out), NR_ERR_ARG,
              "spmm_blocked: null pointer argument");
   NR_REQUIRE((d_sum_out == nullptr) || (d_sum_in != nullptr), NR_ERR_ARG,
              "spmm_blocked: sum_out needs sum_in");
+  NR_REQUIRE(!d_addend_row_flag || (d_addend && !d_x_row_nonzero && !d_y_row_wanted), NR_ERR_ARG,
+             "spmm_blocked: addend row flags need an addend and no masks");
+  const uint8_t* addend_flag = s_addend_by_flag ? d_addend_row_flag : nullptr;
   const BlockedPlan* p = (const BlockedPlan*)plan;
   hipStream_t st = (hipStream_t)stream;
   dim3 grid((unsigned)p->n_wg), block(p->waves * NR_WAVE);
@@ -1467,7 +1504,7 @@ int nrhip_spmm_blocked(const void* plan, const int32_t* d_indices, const float* 
                      p->wg_nrows, p->wg_ent_off, p->wg_cmb_off, p->ent, p->cmb, p->n_phases,        \
                      p->pk_idx, p->pk_val, (const float4*)d_X, (float4*)d_Y, (const float4*)d_addend, \
                      (const float4*)d_sum_in, (float4*)d_sum_out, d_x_row_nonzero, d_y_row_wanted,  \
-                     p->r_max, AdamEpilogue{}, p->row_of, p->p_max)
+                     p->r_max, AdamEpilogue{}, p->row_of, p->p_max, addend_flag)
 #define NR_BLK_D(DD)                                                                               \
   if (p->waves == 16) {                                                                            \
     if (masked) { if (gif == 4) NR_BLK(true, 16, 4, DD); else NR_BLK(true, 16, 8, DD); }           \
@@ -1649,7 +1686,7 @@ int nrhip_spmm_blocked_adam(const void* plan, const int32_t* d_indices, const fl
                      p->wg_ent_off, p->wg_cmb_off, p->ent, p->cmb, p->n_phases, p->pk_idx, p->pk_val,
                      (const float4*)d_X, (float4*)nullptr, (const float4*)d_addend,
                      (const float4*)nullptr, (float4*)nullptr, (const uint8_t*)nullptr,
-                     (const uint8_t*)nullptr, p->r_max, ad, p->row_of, p->p_max);
+                     (const uint8_t*)nullptr, p->r_max, ad, p->row_of, p->p_max, (const uint8_t*)nullptr);
   NR_LAUNCH_CHECK();
   return NR_OK;
 }

@@ -208,8 +208,11 @@ static int lightgcn_fwd_bwd(const nrhip_lightgcn_buffers& b, const int32_t* d_us
                                    nullptr, d, gping[k & 1], b.H, nullptr, nullptr, b.spmm_ws,
                                    b.spmm_ws_bytes, stream));
     else
-      NR_TRY(nrhip_spmm_csr(b.plan_t, b.indptr_t, b.indices_t, b.vals_t, g, d, gping[k & 1], b.H,
-                            nullptr, nullptr, b.spmm_ws, b.spmm_ws_bytes, stream));
+      // H is non-zero on the batch rows only, and their flags stand until the step's last hop (or rows_clear)
+      // re-arms them: the d = 64 lane-group pass reads the flagged rows of H instead of all 18 MB of it
+      NR_TRY(nrhip_spmm_csr_flagged(b.plan_t, b.indptr_t, b.indices_t, b.vals_t, g, d, gping[k & 1], b.H,
+                                    d == 64 && k >= 1 ? b.row_flag : nullptr, nullptr, nullptr, b.spmm_ws,
+                                    b.spmm_ws_bytes, stream));
     g = gping[k & 1];
   }
   *g_out = g;

@@ -1019,14 +1019,24 @@ class SpmmCSR:
         return self._ws[d]
 
     def matmul(self, X, out=None, addend=None, sum_in=None, sum_out=None, x_row_nonzero=None,
-               y_row_wanted=None):
+               y_row_wanted=None, addend_row_flag=None):
         """out = A @ X (+ addend); sum_out = sum_in + out (each optional).
         x_row_nonzero: optional uint8 [n_cols]; 0 promises that row of X is all zero (skipped).
-        y_row_wanted: optional uint8 [n_rows]; rows with 0 are not produced (left untouched)."""
+        y_row_wanted: optional uint8 [n_rows]; rows with 0 are not produced (left untouched).
+        addend_row_flag: optional uint8 [n_rows], unmasked products only; 0 promises that row of addend is all zero
+        (the lane-group pass does not read it)."""
         d = X.shape[1]
         self.ensure_schedule(d)
         ws = self._workspace(d)
-        if x_row_nonzero is None and y_row_wanted is None:
+        if addend_row_flag is not None:
+            if x_row_nonzero is not None or y_row_wanted is not None:
+                raise ValueError("addend_row_flag goes with the unmasked product")
+            call("nrhip_spmm_csr_flagged", self.plan, _ptr(self.indptr), _ptr(self.indices),
+                 _ptr(self.vals), _ptr(X, torch.float32), d,
+                 _ptr(out, torch.float32, allow_none=True), _ptr(addend, allow_none=True),
+                 _ptr(addend_row_flag, torch.uint8), _ptr(sum_in, allow_none=True),
+                 _ptr(sum_out, allow_none=True), _ptr(ws), ws.numel(), _stream())
+        elif x_row_nonzero is None and y_row_wanted is None:
             call("nrhip_spmm_csr", self.plan, _ptr(self.indptr), _ptr(self.indices),
                  _ptr(self.vals), _ptr(X, torch.float32), d,
                  _ptr(out, torch.float32, allow_none=True), _ptr(addend, allow_none=True),
