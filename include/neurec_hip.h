@@ -477,6 +477,22 @@ int nrhip_spmm_blocked_tune_store(int masked_store);
  * caller that rewrites d_vals IN PLACE must call nrhip_spmm_blocked_pack again before the next product
  * (engine.SpmmCSR.values_changed does; NGCF's node dropout is the one such caller). */
 int nrhip_spmm_blocked_pack(void* plan, const int32_t* d_indices, const float* d_vals, void* stream);
+/* nrhip_spmm_blocked_pack, and where the values factor also a 4-byte form of the same pairs, which
+ * spmm_blocked_kernel (the full passes, the pass with ApplyAdam, the general masked form) then reads instead, half
+ * the bytes: word = column | code << column bits, value = float32(factor of the row * table[code]).  The staged
+ * masked hop and the wanted-rows hops keep reading (column, value) pairs.  h_row_factor [n_rows] / h_col_factor [n_cols] are HOST arrays
+ * (graph.factor_values; both NULL: the plain pack) that promise float32(h_row_factor[r] * h_col_factor[c]) ==
+ * value[r][c]; the promise is checked on the device for every non-zero, so results keep every bit.  *packed
+ * (optional) / nrhip_spmm_blocked_is_packed say whether the words are in use.  They are not — the plan is exactly what
+ * the plain pack leaves — when one product misses its value, when there are more than 1,024 distinct factors (the
+ * table the kernels keep in LDS) or more than the word has bits for, or when n_cols > n_rows.  Synchronises the
+ * stream.  nrhip_spmm_blocked_tune_packed(0), process-wide, for tests and A/B runs: read the two arrays of
+ * a packed plan (1: the words again; NEUREC_SPMM_PACKED=0 in the environment of a plan's creation does the same). */
+int nrhip_spmm_blocked_pack_factored(void* plan, const int32_t* d_indices, const float* d_vals,
+                                     const float* h_row_factor, const float* h_col_factor, int64_t n_cols,
+                                     void* stream, int* packed);
+int nrhip_spmm_blocked_is_packed(const void* plan);
+int nrhip_spmm_blocked_tune_packed(int on);
 int nrhip_spmm_blocked(const void* plan, const int32_t* d_indices, const float* d_vals,
                        const float* d_X, float* d_Y, const float* d_addend, const float* d_sum_in,
                        float* d_sum_out, const uint8_t* d_x_row_nonzero,

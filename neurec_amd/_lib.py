@@ -361,6 +361,9 @@ SIGNATURES = {
                              p, sz, p],
     "nrhip_spmm_blocked_plan_bytes": [i64, i64, i32, psz],
     "nrhip_spmm_blocked_pack": [p, p, p, p],
+    "nrhip_spmm_blocked_pack_factored": [p, p, p, p, p, i64, p, C.POINTER(i32)],
+    "nrhip_spmm_blocked_is_packed": [p],
+    "nrhip_spmm_blocked_tune_packed": [i32],
     "nrhip_spmm_blocked_plan_create": [p, p, i64, i64, i32, i64, i32, i32, i32, i32, i32, p, sz, p,
                                        C.POINTER(p)],
     "nrhip_spmm_blocked_plan_destroy": [p],

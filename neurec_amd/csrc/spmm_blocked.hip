@@ -28,6 +28,7 @@
 // Epilogue as in spmm.hip: y += addend, sum_out = sum_in + y.
 #include "nr_common.h"
 #include "spmm_blocked_plan.h"
+#include "spmm_blocked_factor.h"
 #include "spmm_wanted_plan.h"
 #include <algorithm>
 #include <new>
@@ -46,6 +47,7 @@ static_assert((int)nr_plan::kOk == NR_OK && (int)nr_plan::kErrArg == NR_ERR_ARG 
 // layout of the buffer is listed) and the scalars the launches need.
 struct BlockedPlan : nr_plan::PlanArrays<int4> {
   int64_t n_rows, nnz, n_ent, n_cmb;
+  int pk_on, pk_codes, pk_col_bits;   // the 4-byte words stand for the packed pairs (verified); table entries; column bits
   int n_wg, n_phases;
   int seg, r_max, p_max, waves, d;
   const int32_t* pk_from_idx;   // the CSR arrays the packed copy was made from (nullptr: not yet)
@@ -95,6 +97,15 @@ struct AdamEpilogue {
   float4* addend_rw; float4* grad_b_rw; uint8_t* flag_rw;
 };
 
+
+// The packed pairs as 4-byte words (spmm_blocked_factor.h), handed to the kernels that walk the plan's schedule:
+// word = column | code << col_bits, value = __fmul_rn(factor of the sub-list's row, table[code]) — verified equal to
+// the stored value for every non-zero when the plan was packed.  word == nullptr: the two arrays are read.
+static_assert(nr_plan::kMaxFactorCodes == 16 * NR_WAVE, "a 16-wave workgroup stages the factor table one entry per thread");
+struct PackedNz {
+  const uint32_t* word; const float* ent_rf; const float* table;
+  int n_codes, col_bits;
+};
 
 // An entry of the workgroup's staged row list: the row, and in the sign bit "this row's flag is 0" (rows are < 2^31).
 constexpr int kRowBits = 0x7FFFFFFF;
@@ -186,7 +197,7 @@ __global__ __launch_bounds__(kWaves* NR_WAVE) void spmm_blocked_kernel(
     const float4* __restrict__ X, float4* __restrict__ Y, const float4* __restrict__ addend,
     const float4* sum_in, float4* sum_out, const uint8_t* __restrict__ col_mask,
     const uint8_t* __restrict__ row_mask, int kRMax, AdamEpilogue ad, const int32_t* __restrict__ row_of,
-    int kPMax, const uint8_t* __restrict__ addend_flag) {
+    int kPMax, const uint8_t* __restrict__ addend_flag, PackedNz pk) {
   constexpr int LPR = D / 4;                   // lanes per row: 16-byte pieces of a d-float row
   constexpr int GPW = NR_WAVE / LPR;           // lane groups (rows in flight) per wave: 4 / 2 / 1
   constexpr int kGroups = kWaves * GPW;
@@ -202,6 +213,20 @@ __global__ __launch_bounds__(kWaves* NR_WAVE) void spmm_blocked_kernel(
   NR_BLK_STAMP(0);
   const int r0 = wg_row0[wg], nr = wg_nrows[wg];
   int32_t* s_rows = (int32_t*)(s_acc + (size_t)(kRMax + kPMax) * LPR);
+  // packed non-zeros (workgroup-uniform): `indices` holds the words, `vals` is not read, the factor table sits in
+  // LDS behind the row list.  A lane decodes the entries it carries, once each, before the shuffles broadcast them.
+  const bool packed = pk.word != nullptr;
+  if (packed) indices = (const int32_t*)pk.word;
+  float* s_tab = (float*)(s_rows + kRMax);
+  const uint32_t cmask = (1u << pk.col_bits) - 1u;
+  // the table's loads go out first and land in LDS behind the row list's: one round trip under the others, not one more
+  constexpr int kTabPer = nr_plan::kMaxFactorCodes / (kWaves * NR_WAVE);
+  float tab_v[kTabPer];
+#pragma unroll
+  for (int j = 0; j < kTabPer; ++j) {
+    tab_v[j] = 0.f;
+    if (packed && tid + j * kWaves * NR_WAVE < pk.n_codes) tab_v[j] = pk.table[tid + j * kWaves * NR_WAVE];
+  }
   // the row list, read back in the epilogue, and with it the rows' flags (addend_flag: 0 = the addend row is zero
   // and is not read; the Adam pass takes the step's own flags): one byte gather per row here, none in the epilogue
   const uint8_t* fl = ADAM ? ad.flag_rw : addend_flag;                           // workgroup-uniform
@@ -213,6 +238,9 @@ __global__ __launch_bounds__(kWaves* NR_WAVE) void spmm_blocked_kernel(
     s_rows[i] = row;
   }
   for (int i = tid; i < nr * LPR; i += kWaves * NR_WAVE) s_acc[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+  for (int j = 0; j < kTabPer; ++j)
+    if (packed && tid + j * kWaves * NR_WAVE < pk.n_codes) s_tab[tid + j * kWaves * NR_WAVE] = tab_v[j];
   __syncthreads();
   NR_BLK_STAMP(1);
   const int32_t* eoff = wg_ent_off + (int64_t)wg * (n_phases + 1);
@@ -225,7 +253,11 @@ __global__ __launch_bounds__(kWaves* NR_WAVE) void spmm_blocked_kernel(
     // gather round trip, not three dependent ones.
     int ei = e0 + wave * GPW + g;
     int4 cur = make_int4(0, 0, 0, 0);
-    if (ei < e1) cur = ent[ei];
+    float cur_rf = 0.f;                              // the factor of the entry's row: read beside the descriptor
+    if (ei < e1) {
+      cur = ent[ei];
+      if (packed) cur_rf = pk.ent_rf[ei];
+    }
     int cur_idx[IPL];
     float cur_val[IPL];
 #pragma unroll
@@ -234,7 +266,7 @@ __global__ __launch_bounds__(kWaves* NR_WAVE) void spmm_blocked_kernel(
       cur_val[i] = 0.f;
       if (c < CL && c * IPL + i < cur.y) {
         cur_idx[i] = indices[(uint32_t)cur.z + c * IPL + i];
-        cur_val[i] = vals[(uint32_t)cur.z + c * IPL + i];
+        if (!packed) cur_val[i] = vals[(uint32_t)cur.z + c * IPL + i];
       }
     }
     int cur_want = 1;                                // row filter of the current entry (prefetched)
@@ -245,7 +277,11 @@ __global__ __launch_bounds__(kWaves* NR_WAVE) void spmm_blocked_kernel(
       const bool live = ei < e1;
       const int ein = ei + kGroups;
       int4 nxt = make_int4(0, 0, 0, 0);
-      if (ein < e1) nxt = ent[ein];
+      float nxt_rf = 0.f;
+      if (ein < e1) {
+        nxt = ent[ein];
+        if (packed) nxt_rf = pk.ent_rf[ein];
+      }
       const int slot = cur.x;
       int len = cur.y;
       const uint32_t begin = (uint32_t)cur.z;
@@ -274,6 +310,11 @@ __global__ __launch_bounds__(kWaves* NR_WAVE) void spmm_blocked_kernel(
         for (int i = 0; i < IPL; ++i) {
           my_idx[i] = k0 == 0 ? cur_idx[i] : ch_idx[i];
           my_val[i] = k0 == 0 ? cur_val[i] : ch_val[i];
+          if (packed) {                              // entries past the end hold word 0: never used (on[] / nn)
+            const uint32_t w = (uint32_t)my_idx[i];
+            my_idx[i] = (int)(w & cmask);
+            my_val[i] = __fmul_rn(cur_rf, s_tab[w >> pk.col_bits]);
+          }
           if constexpr (MASKED) {
             if (col_mask && c < CL && k0 + c * IPL + i < len && col_mask[my_idx[i]] == 0)
               my_idx[i] = -1;                        // X row all zero
@@ -308,7 +349,7 @@ __global__ __launch_bounds__(kWaves* NR_WAVE) void spmm_blocked_kernel(
               ch_val[i] = 0.f;
               if (c < CL && k0 + 16 + c * IPL + i < len) {
                 ch_idx[i] = indices[begin + k0 + 16 + c * IPL + i];
-                ch_val[i] = vals[begin + k0 + 16 + c * IPL + i];
+                if (!packed) ch_val[i] = vals[begin + k0 + 16 + c * IPL + i];
               }
             }
           }
@@ -317,7 +358,7 @@ __global__ __launch_bounds__(kWaves* NR_WAVE) void spmm_blocked_kernel(
             for (int i = 0; i < IPL; ++i)
               if (c < CL && c * IPL + i < nxt.y) {
                 nxt_idx[i] = indices[(uint32_t)nxt.z + c * IPL + i];
-                nxt_val[i] = vals[(uint32_t)nxt.z + c * IPL + i];
+                if (!packed) nxt_val[i] = vals[(uint32_t)nxt.z + c * IPL + i];
               }
             if constexpr (MASKED) {
               if (row_mask && ein < e1) nxt_want = row_mask[nxt.w];
@@ -335,6 +376,7 @@ __global__ __launch_bounds__(kWaves* NR_WAVE) void spmm_blocked_kernel(
       }
       if (live) s_acc[slot * LPR + c] = acc;
       cur = nxt;
+      cur_rf = nxt_rf;
 #pragma unroll
       for (int i = 0; i < IPL; ++i) { cur_idx[i] = nxt_idx[i]; cur_val[i] = nxt_val[i]; }
       cur_want = nxt_want;
@@ -1229,6 +1271,17 @@ int s_gathers_in_flight = 8;     // tuning knob (nrhip_spmm_blocked_tune)
 constexpr int kMaskedStoreDefault = kStoreWt;
 int s_addend_by_flag = 1;        // tuning knob (nrhip_spmm_blocked_tune_addend_flag): 0 reads a flagged addend densely
 int s_masked_store = kMaskedStoreDefault;   // tuning knob (nrhip_spmm_blocked_tune_store): how the column-masked hop stores Y
+int s_packed = 1;                // tuning knob (nrhip_spmm_blocked_tune_packed): 0 reads the two arrays of a packed plan
+
+// The words of a packed plan for spmm_blocked_kernel, or the "read the two arrays" form.  extra_lds: the factor
+// table behind what the kernel has in LDS already.
+PackedNz packed_for(const BlockedPlan* p, size_t lds, size_t* extra_lds) {
+  *extra_lds = 0;
+  const size_t tab = (size_t)p->pk_codes * 4;
+  if (!p->pk_on || !s_packed || lds + tab > (size_t)kMaxLdsBytes) return PackedNz{nullptr, nullptr, nullptr, 0, 0};
+  *extra_lds = tab;
+  return PackedNz{p->pk_word, p->ent_rf, p->pk_table, p->pk_codes, p->pk_col_bits};
+}
 
 // (column, value) pairs copied into the plan's row order: row k of the order is CSR positions
 // [src[k], src[k] + dst[k+1] - dst[k]) -> packed positions [dst[k], dst[k+1]).  Once per matrix.
@@ -1246,13 +1299,54 @@ __global__ __launch_bounds__(256) void row_order_pack_kernel(const uint32_t* __r
   }
 }
 
+// The same pairs as words (spmm_blocked_factor.h), every one checked: the product the kernels will form must have
+// the stored value's bits, and the column must be one the codes cover.  A miss sets *bad; the plan then stays on
+// the two arrays.  code[0 .. n_rows) row codes, code[n_rows ..) column codes.
+__global__ __launch_bounds__(256) void row_order_pack_words_kernel(
+    const uint32_t* __restrict__ src, const uint32_t* __restrict__ dst, const int32_t* __restrict__ row_of,
+    int64_t n_rows, int64_t n_cols, const int32_t* __restrict__ indices, const float* __restrict__ vals,
+    const uint16_t* __restrict__ code, const float* __restrict__ table, int col_bits, uint32_t* __restrict__ pk_word,
+    uint32_t* __restrict__ bad) {
+  const int c = threadIdx.x & 15;
+  bool miss = false;
+  for (int64_t k = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4); k < n_rows; k += (int64_t)gridDim.x * 16) {
+    const uint32_t s0 = src[k], d0 = dst[k], len = dst[k + 1] - d0;
+    const float rf = table[code[row_of[k]]];
+    for (uint32_t j = c; j < len; j += 16) {
+      const int32_t col = indices[s0 + j];
+      uint32_t w = 0;
+      if (col < 0 || col >= n_cols) {
+        miss = true;
+      } else {
+        const uint32_t cc = code[n_rows + col];
+        if (__float_as_uint(__fmul_rn(rf, table[cc])) != __float_as_uint(vals[s0 + j])) miss = true;
+        w = (uint32_t)col | (cc << col_bits);
+      }
+      pk_word[d0 + j] = w;
+    }
+  }
+  if (miss) *bad = 1u;
+}
+
+// the factor of every descriptor's row, beside the descriptor
+__global__ __launch_bounds__(256) void entry_row_factor_kernel(const int4* __restrict__ ent, int64_t n_ent,
+                                                               const uint16_t* __restrict__ code,
+                                                               const float* __restrict__ table,
+                                                               float* __restrict__ ent_rf) {
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n_ent; e += (int64_t)gridDim.x * 256)
+    ent_rf[e] = table[code[ent[e].w]];
+}
+
 // The kernels of this plan's width may use the LDS their schedule needs (more than the 64 KB a kernel gets unasked).
 static hipError_t allow_plan_lds(const BlockedPlan* p) {
   hipError_t e = hipSuccess;
   auto allow = [&](const void* fn, size_t lds) {
     if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   };
-  const size_t lds = (size_t)(p->r_max + p->p_max) * p->d * 4 + (size_t)p->r_max * 4;   // accumulators + the workgroup's row list
+  // accumulators + the workgroup's row list + the factor table of a packed plan, where it fits
+  const size_t tab = (size_t)nr_plan::kMaxFactorCodes * 4;
+  size_t lds = (size_t)(p->r_max + p->p_max) * p->d * 4 + (size_t)p->r_max * 4;
+  if (lds + tab <= (size_t)kMaxLdsBytes) lds += tab;
 #define NR_ALLOW(DD)                                                                                                         \
   allow((const void*)spmm_blocked_kernel<false, 16, 8, DD>, lds); allow((const void*)spmm_blocked_kernel<true, 16, 8, DD>, lds); \
   allow((const void*)spmm_blocked_kernel<false, 16, 4, DD>, lds); allow((const void*)spmm_blocked_kernel<true, 16, 4, DD>, lds); \
@@ -1320,6 +1414,8 @@ int nrhip_spmm_blocked_plan_create(const int64_t* h_indptr, const int32_t* h_ind
   opt.masked_fast = !(env && env[0] == '0');
   env = getenv("NEUREC_SPMM_WANTED_WAVE");
   opt.wanted_wave = !(env && env[0] == '0');
+  env = getenv("NEUREC_SPMM_PACKED");                        // A/B runs of whole programs: nrhip_spmm_blocked_tune_packed
+  if (env) s_packed = env[0] != '0';
   env = getenv("NEUREC_SPMM_WANTED_NNZ_CAP");                // tests: force the chunked path
   opt.wanted_nnz_cap = env ? std::max(atoi(env), 1) : 0;
 
@@ -1340,6 +1436,7 @@ int nrhip_spmm_blocked_plan_create(const int64_t* h_indptr, const int32_t* h_ind
   p->wp_ok = h.ww_ok && opt.seg == nr_wplan::kSeg && n_rows <= nr_wplan::kMaxRows && !(env && env[0] == '0');
   if (p->wp_ok) p->wp_profile = nr_wplan::slot_profile(h_indptr, n_rows);
   std::vector<nr_plan::Section> sections = nr_plan::plan_sections(*p, h);
+  for (const nr_plan::Section& fs : nr_plan::factor_sections(*p, h)) sections.push_back(fs);
   const size_t used = nr_plan::carve_sections(&sections, d_plan_buf);
   if (used > plan_bytes) {
     delete p;
@@ -1378,6 +1475,57 @@ int nrhip_spmm_blocked_pack(void* plan, const int32_t* d_indices, const float* d
   }
   p->pk_from_idx = d_indices;
   p->pk_from_val = d_vals;
+  p->pk_on = 0;                         // the words (if any) stood for the values before this call
+  return NR_OK;
+}
+
+/* nrhip_spmm_blocked_pack, and where the values factor also the 4-byte form of the same pairs: h_row_factor
+ * [n_rows] and h_col_factor [n_cols] (host; both NULL: the plain pack) promise
+ * float32(h_row_factor[r] * h_col_factor[c]) == value[r][c], which is checked on the device for every non-zero.
+ * *packed (optional) says whether the kernels will read the words.  They do not, and the plan stays exactly as the
+ * plain pack leaves it, when one product misses its value, when there are more distinct factors than the table in
+ * LDS holds (1,024) or than the word has bits for beside the column, or when the matrix has more columns than rows
+ * (the pack's code scratch is sized by the rows).  Synchronises the stream (init-time). */
+int nrhip_spmm_blocked_pack_factored(void* plan, const int32_t* d_indices, const float* d_vals,
+                                     const float* h_row_factor, const float* h_col_factor, int64_t n_cols,
+                                     void* stream, int* packed) {
+  if (packed) *packed = 0;
+  NR_TRY(nrhip_spmm_blocked_pack(plan, d_indices, d_vals, stream));
+  BlockedPlan* p = (BlockedPlan*)plan;
+  if (!h_row_factor || !h_col_factor || p->nnz == 0 || n_cols <= 0 || n_cols > p->n_rows) return NR_OK;
+  nr_plan::FactorLayout lay;
+  nr_plan::Error err;
+  if (nr_plan::factor_layout(h_row_factor, p->n_rows, h_col_factor, n_cols, &lay, &err) != nr_plan::kOk) return NR_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const uint32_t zero = 0;
+  NR_CHECK_HIP(hipMemcpyAsync(p->pk_table, lay.table.data(), lay.table.size() * 4, hipMemcpyHostToDevice, st));
+  NR_CHECK_HIP(hipMemcpyAsync(p->pk_code, lay.row_code.data(), (size_t)p->n_rows * 2, hipMemcpyHostToDevice, st));
+  NR_CHECK_HIP(hipMemcpyAsync(p->pk_code + p->n_rows, lay.col_code.data(), (size_t)n_cols * 2, hipMemcpyHostToDevice, st));
+  NR_CHECK_HIP(hipMemcpyAsync(p->pk_bad, &zero, 4, hipMemcpyHostToDevice, st));
+  const unsigned blocks = (unsigned)std::min<int64_t>((p->n_rows + 15) / 16, 8192);
+  hipLaunchKernelGGL(row_order_pack_words_kernel, dim3(blocks), dim3(256), 0, st, p->pk_src, p->pk_dst, p->row_of,
+                     p->n_rows, n_cols, d_indices, d_vals, p->pk_code, p->pk_table, lay.col_bits, p->pk_word, p->pk_bad);
+  NR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(entry_row_factor_kernel, dim3((unsigned)std::min<int64_t>((p->n_ent + 255) / 256, 8192)),
+                     dim3(256), 0, st, p->ent, p->n_ent, p->pk_code, p->pk_table, p->ent_rf);
+  NR_LAUNCH_CHECK();
+  uint32_t bad = 1;
+  NR_CHECK_HIP(hipMemcpyAsync(&bad, p->pk_bad, 4, hipMemcpyDeviceToHost, st));
+  NR_CHECK_HIP(hipStreamSynchronize(st));
+  if (bad) return NR_OK;
+  p->pk_codes = (int)lay.table.size();
+  p->pk_col_bits = lay.col_bits;
+  p->pk_on = 1;
+  if (packed) *packed = 1;
+  return NR_OK;
+}
+
+int nrhip_spmm_blocked_is_packed(const void* plan) {
+  return plan && ((const BlockedPlan*)plan)->pk_on ? 1 : 0;
+}
+
+int nrhip_spmm_blocked_tune_packed(int on) {
+  s_packed = on ? 1 : 0;
   return NR_OK;
 }
 
@@ -1499,12 +1647,14 @@ int nrhip_spmm_blocked_flagged(const void* plan, const int32_t* d_indices, const
     NR_LAUNCH_CHECK();
     return NR_OK;
   }
+  size_t tab_lds = 0;
+  const PackedNz pk = packed_for(p, lds, &tab_lds);
 #define NR_BLK(M, W, GG, DD)                                                                       \
-  hipLaunchKernelGGL((spmm_blocked_kernel<M, W, GG, DD>), grid, block, lds, st, p->wg_row0,        \
+  hipLaunchKernelGGL((spmm_blocked_kernel<M, W, GG, DD>), grid, block, lds + tab_lds, st, p->wg_row0, \
                      p->wg_nrows, p->wg_ent_off, p->wg_cmb_off, p->ent, p->cmb, p->n_phases,        \
                      p->pk_idx, p->pk_val, (const float4*)d_X, (float4*)d_Y, (const float4*)d_addend, \
                      (const float4*)d_sum_in, (float4*)d_sum_out, d_x_row_nonzero, d_y_row_wanted,  \
-                     p->r_max, AdamEpilogue{}, p->row_of, p->p_max, addend_flag)
+                     p->r_max, AdamEpilogue{}, p->row_of, p->p_max, addend_flag, pk)
 #define NR_BLK_D(DD)                                                                               \
   if (p->waves == 16) {                                                                            \
     if (masked) { if (gif == 4) NR_BLK(true, 16, 4, DD); else NR_BLK(true, 16, 8, DD); }           \
@@ -1681,12 +1831,14 @@ int nrhip_spmm_blocked_adam(const void* plan, const int32_t* d_indices, const fl
                   alpha, 1.0f - beta1, 1.0f - beta2, eps,
                   clear_consumed ? (float4*)d_addend : nullptr,
                   clear_consumed ? (float4*)d_grad_b : nullptr, clear_consumed ? d_row_flag : nullptr};
+  size_t tab_lds = 0;
+  const PackedNz pk = packed_for(p, lds, &tab_lds);
   hipLaunchKernelGGL((spmm_blocked_kernel<false, 16, 8, 64, true>), dim3((unsigned)p->n_wg),
-                     dim3(16 * NR_WAVE), lds, (hipStream_t)stream, p->wg_row0, p->wg_nrows,
+                     dim3(16 * NR_WAVE), lds + tab_lds, (hipStream_t)stream, p->wg_row0, p->wg_nrows,
                      p->wg_ent_off, p->wg_cmb_off, p->ent, p->cmb, p->n_phases, p->pk_idx, p->pk_val,
                      (const float4*)d_X, (float4*)nullptr, (const float4*)d_addend,
                      (const float4*)nullptr, (float4*)nullptr, (const uint8_t*)nullptr,
-                     (const uint8_t*)nullptr, p->r_max, ad, p->row_of, p->p_max, (const uint8_t*)nullptr);
+                     (const uint8_t*)nullptr, p->r_max, ad, p->row_of, p->p_max, (const uint8_t*)nullptr, pk);
   NR_LAUNCH_CHECK();
   return NR_OK;
 }

@@ -29,6 +29,7 @@ constexpr int kRMaxDefault = 416;   // row accumulators per workgroup (104 KB)
 constexpr int kPMaxDefault = 192;   // segment partial slots per workgroup and phase (48 KB)
 constexpr int kMaxPhases = 32;
 constexpr int kMaxLdsBytes = 160 * 1024;
+constexpr int kPlanFactorCodes = 1024;   // entries of the factor table (spmm_blocked_factor.h: kMaxFactorCodes)
 constexpr int kWaveChunk = 8;       // wave-cooperative wanted-rows hop: 64-segments per chunk of a hub row
 
 // what the kernels read as int4 (uploaded as bytes)
@@ -520,6 +521,12 @@ struct PlanArrays {
   // staged masked kernel reads it in bulk).  ent[].z / wg_nnz index the packed arrays.
   int32_t* row_of; uint32_t* pk_src; uint32_t* pk_dst;
   int32_t* pk_idx; float* pk_val;          // [nnz] filled on the device (nrhip_spmm_blocked_pack)
+  // the same pairs as 4-byte words (spmm_blocked_factor.h), when the values factor (nrhip_spmm_blocked_pack_factored):
+  uint32_t* pk_word;                       // [nnz] column | code of the column's factor
+  float* ent_rf;                           // [entries] the factor of the descriptor's row
+  float* pk_table;                         // [kMaxFactorCodes] distinct factors
+  uint16_t* pk_code;                       // [2 * n_rows] scratch of the pack: row codes, then column codes
+  uint32_t* pk_bad;                        // [1] set by the pack's check when a product misses its value
   int32_t* wg_ent_off; int32_t* wg_cmb_off;
   uint32_t* wg_nnz;
   I4* w_ent; I4* w_cmb; int32_t* w_ent_off; int32_t* w_cmb_off;
@@ -584,6 +591,19 @@ std::vector<Section> plan_sections(PlanArrays<I4>& p, const Plan& h) {
   return s;
 }
 
+// The sections of the 4-byte non-zeros (spmm_blocked_factor.h), carved behind plan_sections' by the plan's creator;
+// nothing is uploaded (nrhip_spmm_blocked_pack_factored fills them on the device).
+template <class I4>
+std::vector<Section> factor_sections(PlanArrays<I4>& p, const Plan& h) {
+  return {
+      section(p.pk_word, nullptr, (size_t)h.nnz * 4, 4),
+      section(p.ent_rf, nullptr, h.ent.size() * 4, 4),
+      section(p.pk_table, nullptr, (size_t)kPlanFactorCodes * 4),
+      section(p.pk_code, nullptr, (size_t)h.n_rows * 4),
+      section(p.pk_bad, nullptr, 4, 0, true),
+  };
+}
+
 // gives every section its address in the buffer at `base`; returns the bytes used
 inline size_t carve_sections(std::vector<Section>* sections, void* base) {
   size_t off = 0;
@@ -611,7 +631,9 @@ inline size_t blocked_plan_bytes(int64_t n_rows, int64_t nnz) {
                     2 * align_up(max_cmb * 16 + 16, 256) /* ww_hub, ww_lcmb */ +
                     align_up(ww_seg * 256 + 256, 256) /* ww_part */ + align_up(max_cmb * 4 + 4, 256) /* ww_cnt */;
   const size_t dealt = 3 * align_up(((size_t)n_rows + 1) * 4, 256) /* row_of, pk_src, pk_dst */ +
-                       2 * align_up((size_t)nnz * 4 + 4, 256) /* pk_idx, pk_val */;
+                       3 * align_up((size_t)nnz * 4 + 4, 256) /* pk_idx, pk_val, pk_word */ +
+                       align_up(max_ent * 4 + 4, 256) /* ent_rf */ + align_up((size_t)kPlanFactorCodes * 4, 256) +
+                       align_up((size_t)n_rows * 4, 256) /* pk_code */ + 256 /* pk_bad */;
   return ww + dealt + align_up(max_ent * 16, 256) /* ent */ + align_up(max_cmb * 16, 256) /* cmb */ +
          3 * align_up(wg * 8, 256) /* wg_row0, wg_nrows, wg_nnz */ +
          2 * align_up(wg * (kMaxPhases + 1) * 4, 256) /* wg_ent_off, wg_cmb_off */ +

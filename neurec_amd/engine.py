@@ -11,7 +11,10 @@ import os
 import numpy as np
 import torch
 
+import scipy.sparse as _sp
+
 from . import _lib
+from . import graph as _graph
 from ._lib import call
 
 NGCF_MAX_LAYERS = _lib.NGCF_MAX_LAYERS
@@ -902,6 +905,9 @@ def div_scalar(x, denom, out):
     call("nrhip_div_scalar", _ptr(x), float(denom), _ptr(out), x.numel(), _stream())
 
 
+_UNSET = object()
+
+
 class SpmmCSR:
     """A CSR matrix resident on the device plus its row-segment plan."""
 
@@ -913,11 +919,15 @@ class SpmmCSR:
             self.indices = indices.to(dev, torch.int32).contiguous()
             self.vals = vals.to(dev, torch.float32).contiguous()
             self._h_indices = None                     # fetched only if a lane-group schedule is built
+            self._host_built = False
         else:
             self.h_indptr = np.ascontiguousarray(indptr, dtype=np.int64)
             idx = np.ascontiguousarray(indices, dtype=np.int32)
             val = np.ascontiguousarray(vals, dtype=np.float32)
             self._h_indices = idx
+            self._host_built = True
+            self._h_factors = _UNSET                   # graph.factor_values of the current values, found on first use
+            self._h_vals = val
             self.indices = torch.from_numpy(idx if len(idx) else np.zeros(1, np.int32)).to(dev)
             self.vals = torch.from_numpy(val if len(val) else np.zeros(1, np.float32)).to(dev)
             self.indptr = torch.from_numpy(self.h_indptr).to(dev)
@@ -992,19 +1002,44 @@ class SpmmCSR:
                          0, 0, 0, 0, 0, 0, _ptr(buf), buf.numel(), _stream(), C.byref(plan))
                     call("nrhip_spmm_plan_attach_blocked", self.plan, plan, d)
                     # the plan's own copy of the (column, value) pairs, in its row order: filled once
-                    call("nrhip_spmm_blocked_pack", plan, _ptr(self.indices), _ptr(self.vals), _stream())
+                    self._pack(plan)
                     self._blocked[d] = (plan, buf)
                 except NotImplementedError:
                     pass                   # does not fit the schedule: work-item kernel stays
         self.blocked = self._blocked[d][0]
         return self.blocked is not None
 
-    def values_changed(self):
+    def _pack(self, plan):
+        """the plan's copy of the pairs; for a host-built matrix whose values factor (graph.factor_values) also the
+        4-byte form spmm_blocked_kernel reads (nrhip_spmm_blocked_pack_factored)"""
+        if self._host_built and self._h_factors is _UNSET:
+            self._h_factors = _graph.factor_values(
+                _sp.csr_matrix((self._h_vals, self._h_indices, self.h_indptr), shape=(self.n_rows, self.n_cols))) \
+                if self.nnz > 0 and self.n_cols <= self.n_rows else None
+            self._h_vals = None
+        if not self._host_built or self._h_factors is None:
+            call("nrhip_spmm_blocked_pack", plan, _ptr(self.indices), _ptr(self.vals), _stream())
+            return
+        rf, cf = (np.ascontiguousarray(f, dtype=np.float32) for f in self._h_factors)
+        call("nrhip_spmm_blocked_pack_factored", plan, _ptr(self.indices), _ptr(self.vals),
+             rf.ctypes.data_as(C.c_void_p), cf.ctypes.data_as(C.c_void_p), self.n_cols, _stream(), None)
+
+    def is_packed(self, d):
+        """does the width-d lane-group schedule read the 4-byte non-zeros?"""
+        return bool(self.ensure_schedule(d) and _lib.lib.nrhip_spmm_blocked_is_packed(self.blocked))
+
+    def values_changed(self, factor=True):
         """`vals` was rewritten in place (NGCF's node dropout): the lane-group schedules hold their own copy of the
-        (column, value) pairs in schedule order and must re-read it"""
+        (column, value) pairs in schedule order and must re-read it.  factor: look for the factors of the new values
+        (a device-to-host copy; host-built matrices only) — a caller whose new values cannot factor passes False."""
+        if self._host_built:
+            self._h_factors = None
+            if factor and any(plan is not None and plan.value for plan, _buf in self._blocked.values()):
+                self._h_vals = self.vals[:self.nnz].cpu().numpy()
+                self._h_factors = _UNSET
         for plan, _buf in self._blocked.values():
             if plan is not None and plan.value:
-                call("nrhip_spmm_blocked_pack", plan, _ptr(self.indices), _ptr(self.vals), _stream())
+                self._pack(plan)
 
     def exact_row_nnz(self, d):
         """Rows with at most this many non-zeros are summed strictly in ascending column order."""

@@ -106,6 +106,42 @@ def transpose_csr(a):
     return t
 
 
+def factor_values(csr):
+    """(row_factor, col_factor), float32 arrays with float32(row_factor[r] * col_factor[c]) == value[r][c] BIT FOR BIT
+    for every stored entry, or None.  The lane-group SpMM then keeps a 4-byte word per non-zero instead of a column
+    and a value (SpmmCSR.ensure_schedule).  Tried, in this order:
+      * row-constant rows (`plain`, `gcmc`, `norm`, NGCF's `norm` / `gcmc`): the row's value times 1;
+      * the symmetric form of `pre`: dinv[r] * dinv[c], dinv computed from the row lengths the way
+        lightgcn_adjacency computes it (square matrices only).
+    `mean` (a diagonal of 1.0 beside row-constant entries) and arbitrary values give None."""
+    a = csr.tocsr()
+    n_rows, n_cols = a.shape
+    indptr = np.asarray(a.indptr, dtype=np.int64)
+    vals = np.ascontiguousarray(a.data, dtype=np.float32)
+    if len(vals) == 0 or len(vals) != indptr[-1]:
+        return None
+    bits = vals.view(np.uint32)
+    lens = np.diff(indptr)
+    row_of = np.repeat(np.arange(n_rows), lens)
+    cols = np.asarray(a.indices, dtype=np.int64)
+
+    def accepted(rf, cf):
+        with np.errstate(invalid="ignore", over="ignore"):
+            prod = (rf[row_of] * cf[cols]).astype(np.float32)
+        return np.array_equal(prod.view(np.uint32), bits)
+
+    rf = np.zeros(n_rows, np.float32)
+    rf[lens > 0] = vals[indptr[:-1][lens > 0]]
+    cf = np.ones(n_cols, np.float32)
+    if accepted(rf, cf):
+        return rf, cf
+    if n_rows == n_cols:
+        dinv = _inv_power(lens.astype(np.float32), np.float32(-0.5)).astype(np.float32)
+        if accepted(dinv, dinv):
+            return dinv, dinv.copy()
+    return None
+
+
 def is_symmetric(a):
     return (a != a.T).nnz == 0
 

@@ -233,8 +233,8 @@ class NGCFWideEngine:
              1 if given is not None else 0, C.c_uint64(self.seed & (2**64 - 1)), C.c_uint64(self.t), _ptr(self.A.vals),
              _stream())
         call("nrhip_gather_f32", _ptr(self.A.vals), _ptr(self._t_of, torch.int32), n, _ptr(self.At.vals), _stream())
-        self.A.values_changed()
-        self.At.values_changed()
+        self.A.values_changed(factor=False)       # dropped edges: the values no longer factor
+        self.At.values_changed(factor=False)
 
     def step(self, users, pos, neg, loss_out, masks=None, plan=None, node_keep_given=None):
         """One optimiser step: ONE native call (nrhip_ngcf_wide_step enqueues the ~25 + 15 L launches; issued from
