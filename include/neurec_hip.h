@@ -1874,6 +1874,63 @@ int nrhip_gru4rec_user_states(const int64_t* d_seq_ptr, const int32_t* d_seq, in
 int nrhip_gru4rec_scores(const float* d_H, int64_t ldh, const float* d_Q, const float* d_b, int n, int n_items, int d,
                          int final_act, float* d_out, int64_t ld, void* stream);
 
+/* ---- GRU4RecPlus (GRU4Rec with shared sampled negatives and the softmax-weighted max losses) ----------------------
+ * These symbols are additions: no existing struct changes and NRHIP_ABI_VERSION stays 4.
+ * The variables, the cell, the states, nrhip_gru4rec_advance, nrhip_gru4rec_user_states and nrhip_gru4rec_scores are
+ * GRU4Rec's: _get_user_embeddings and predict() of the two reference classes are the same computation.
+ * nrhip_gru4recplus_step replaces one `sess.run([self.update_opt, self.final_state], feed_dict=feed)` of
+ * GRU4RecPlus.py:186 up to the optimiser: the graph of GRU4RecPlus.py:130-150 forward, the loss
+ * (GRU4RecPlus.py:91-120) and every gradient.  d_X holds batch items, d_Y holds M = batch + n_sample: the first batch
+ * are the positives (the positive of row i is column i, tf.eye(b, size_y), GRU4RecPlus.py:93), the rest the sampled
+ * negatives every row shares (GRU4RecPlus.py:178-180).
+ *     Z[i][j] = h_top[i] . Q[Y[j]] + b[Y[j]], [batch][M];  A = final_act(Z);  p = A[i][i]
+ *     hm_j = [j != i];  m = max_j (A[i][j] hm_j);  e_j = hm_j exp(A[i][j] hm_j - m);  s_j = e_j / sum_j e_j
+ *                                                                                         (_softmax_neg, GRU4RecPlus.py:91-98)
+ *     bpr_max   L_i = -log(sum_j s_j sigmoid(p - A[i][j]) + 1e-24) + bpr_reg sum_j s_j A[i][j]^2   (GRU4RecPlus.py:100-110)
+ *     top1_max  L_i = sum_j s_j (sigmoid(A[i][j] - p) + sigmoid(A[i][j]^2))                        (GRU4RecPlus.py:112-120)
+ *     loss = mean_i L_i + reg (l2(E_in[X]) + l2(Q[Y]) + l2(b[Y])), on the GATHERED rows, all M slots (GRU4RecPlus.py:149-150)
+ * The softmax weights s are differentiated (they are no constants); the shift m cancels and is treated as one.
+ * loss_kind: 0 top1_max, 1 bpr_max; hidden_act and final_act as in nrhip_gru4rec_step.
+ * Output as nrhip_gru4rec_step's: d_loss2, d_h_new, the cells' gradients whole, the rows of d_G_Ein / d_G_Q / d_G_b the
+ * batch touched STORED, a row that occurs in several slots as the sum of its slots in slot order.  A slot whose id is
+ * outside [0, n_items) reads a row of zeros (it still takes part in the row's softmax as a zero logit) and its
+ * gradient row is dropped.
+ * Work buffers: d_keys uint64 [2 batch + n_sample]; d_ws float [nrhip_gru4recplus_workspace_floats].  Layers, widths and
+ * batch within GRU4Rec's limits, n_sample 0..NRHIP_GRU4RECPLUS_MAX_SAMPLE (batch + n_sample floats then fit LDS);
+ * outside: NRHIP_ERR_UNSUPPORTED.  n_sample == 0 is legal (GRU4RecPlus.py:178); batch + n_sample < 2 with batch > 0
+ * is refused (NRHIP_ERR_UNSUPPORTED): the reference divides 0 by 0 there.  batch == 0 launches nothing and writes
+ * nothing.  fp32 throughout (the two reported sums are added in double and rounded once), every sum in a fixed order,
+ * no atomics: two calls on the same inputs are bit-identical. */
+#define NRHIP_GRU4RECPLUS_MAX_SAMPLE 8192
+typedef struct nrhip_gru4recplus_step_args {
+  const float* d_Ein;
+  const float* d_Q;
+  const float* d_b;
+  nrhip_gru4rec_weights w;
+  float* d_G_Ein;
+  float* d_G_Q;
+  float* d_G_b;
+  float* d_G_Wg[NRHIP_GRU4REC_MAX_LAYERS];
+  float* d_G_bg[NRHIP_GRU4REC_MAX_LAYERS];
+  float* d_G_Wc[NRHIP_GRU4REC_MAX_LAYERS];
+  float* d_G_bc[NRHIP_GRU4REC_MAX_LAYERS];
+  const float* d_state[NRHIP_GRU4REC_MAX_LAYERS];
+  float* d_h_new[NRHIP_GRU4REC_MAX_LAYERS];
+  const int32_t* d_X;
+  const int32_t* d_Y;
+  uint64_t* d_keys;
+  float* d_ws;
+  float* d_loss2;
+  int n_items, batch, n_sample, final_act, loss_kind;
+  float reg, bpr_reg;
+} nrhip_gru4recplus_step_args;
+/* Replaces the storage TensorFlow gives the intermediate tensors of the graph (GRU4RecPlus.py:130-150) and their
+ * gradients: the size in floats of nrhip_gru4recplus_step's d_ws for batches up to max_batch with n_sample negatives. */
+int nrhip_gru4recplus_workspace_floats(int n_layers, const int* widths, int max_batch, int n_sample, size_t* floats);
+/* Replaces one `sess.run([self.update_opt, self.final_state], feed_dict=feed)` of GRU4RecPlus.py:186 up to the
+ * optimiser; the head of this section has the graph, the outputs and the limits. */
+int nrhip_gru4recplus_step(const nrhip_gru4recplus_step_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

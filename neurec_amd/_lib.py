@@ -244,6 +244,16 @@ class Gru4recStepArgs(C.Structure):
         [(n, C.c_int) for n in ("n_items", "batch", "final_act", "loss_kind")] + [("reg", C.c_float)]
 
 
+class Gru4recplusStepArgs(C.Structure):
+    """nrhip_gru4recplus_step_args (include/neurec_hip.h)"""
+    _fields_ = [(n, C.c_void_p) for n in ("Ein", "Q", "b")] + [("w", Gru4recWeights)] + \
+        [(n, C.c_void_p) for n in ("G_Ein", "G_Q", "G_b")] + \
+        [(n, C.c_void_p * GRU4REC_MAX_LAYERS) for n in ("G_Wg", "G_bg", "G_Wc", "G_bc", "state", "h_new")] + \
+        [(n, C.c_void_p) for n in ("X", "Y", "keys", "ws", "loss2")] + \
+        [(n, C.c_int) for n in ("n_items", "batch", "n_sample", "final_act", "loss_kind")] + \
+        [("reg", C.c_float), ("bpr_reg", C.c_float)]
+
+
 # name -> argtypes; every function returns int status except where noted.
 SIGNATURES = {
     "nrhip_device_info": [C.POINTER(i32), C.POINTER(i32), psz, C.c_char_p, i32],
@@ -454,6 +464,8 @@ SIGNATURES = {
     "nrhip_gru4rec_advance": [C.POINTER(p), C.POINTER(p), C.POINTER(i32), i32, i32, p, p],
     "nrhip_gru4rec_user_states": [p, p, i32, i32, p, p, i32, p, C.POINTER(Gru4recWeights), p, i64, p],
     "nrhip_gru4rec_scores": [p, i64, p, p, i32, i32, i32, i32, p, i64, p],
+    "nrhip_gru4recplus_workspace_floats": [i32, C.POINTER(i32), i32, i32, psz],
+    "nrhip_gru4recplus_step": [C.POINTER(Gru4recplusStepArgs), p],
 }
 
 for _name, _args in SIGNATURES.items():

@@ -55,6 +55,9 @@ MODELS = {
                  ("loss_function", "bpr"), ("init_method", "tnormal"), ("stddev", "0.01"), ("verbose", "1")],
     "GRU4Rec": [("lr", "0.0001"), ("reg", "0.0"), ("layers", "[100]"), ("batch_size", "256"), ("loss", "top1"),
                 ("hidden_act", "tanh"), ("final_act", "linear"), ("epochs", "1000")],
+    "GRU4RecPlus": [("lr", "0.01"), ("reg", "0.0"), ("bpr_reg", "1.0"), ("layers", "[100]"), ("batch_size", "256"),
+                    ("loss", "bpr_max"), ("hidden_act", "tanh"), ("final_act", "linear"), ("n_sample", "2048"),
+                    ("sample_alpha", "0.75"), ("epochs", "1000")],
 }
 
 
