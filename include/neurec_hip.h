@@ -1931,6 +1931,82 @@ int nrhip_gru4recplus_workspace_floats(int n_layers, const int* widths, int max_
  * optimiser; the head of this section has the graph, the outputs and the limits. */
 int nrhip_gru4recplus_step(const nrhip_gru4recplus_step_args* args, void* stream);
 
+/* ---- SASRec (causal multi-head self-attention blocks over padded item sequences) ----------------------------------
+ * These symbols are additions: no existing struct changes and NRHIP_ABI_VERSION stays 4.
+ * nrhip_sasrec_step replaces one `sess.run(self.train_opt, feed_dict=feed)` of SASRec.py:402 up to the optimiser: the
+ * graph of SASRec.py:311-375 forward with training on, the loss and every gradient.  d_seq / d_pos_ids / d_neg_ids are
+ * int32 [batch][L]; the padding item is id n_items (any id outside [0, n_items) reads the zero row, and its gradient is
+ * dropped).
+ *     table = concat(item, zeros[1, d]) sqrt(d);  x = (table[seq] + pos[0..L)) drop_0 * (seq != n_items)
+ *     per block: q = ln1(x);  Q = q Wq + bq, K = x Wk + bk, V = x Wv + bv;  heads along the feature axis;
+ *                logits Q K^T / sqrt(d / h), a key masked where sum(x_j) == 0 or j > i (value -2**32 + 1), softmax,
+ *                * [sum(q_i) != 0], drop, . V;  y = that + q;  u = ln2(y);
+ *                x = (drop(drop(relu(u W1 + b1)) W2 + b2) + u) * (seq != n_items)
+ *     z = lnf(x);  ln(v) = gamma (v - mean) / sqrt(biased var + 1e-8) + beta
+ *     loss = sum_t [pos_t != n_items] (-log(sigmoid(table[pos_t] . z_t) + 1e-24)
+ *                                      - log(1 - sigmoid(table[neg_t] . z_t) + 1e-24)) / sum_t [pos_t != n_items]
+ *            (+ l2_emb (sum item^2 + sum pos^2) / 2 when l2_emb != 0)
+ * Variables of a block, in creation order (d_blk[i][k]): ln1 beta, ln1 gamma, Wq [d][d], bq, Wk, bk, Wv, bv, ln2 beta,
+ * ln2 gamma, W1 [d][d] (the conv1d kernel [1][d][d]), b1, W2, b2.
+ * Dropout: 1 + 3 n_blocks sites in evaluation order (the embedding [B][L][d]; per block the attention weights
+ * [h B][L][L] head-major, the hidden layer and the output of the feed-forward net [B][L][d]).  d_mask[k] != NULL: the
+ * uint8 {0, 1} keep mask of site k (all sites or none); otherwise a counter-based generator keyed by (seed, step, site,
+ * element).  rate 0 applies none.
+ * Output: d_loss2[0] the loss term, d_loss2[1] the regulariser term; every gradient STORED whole (d_G_item must be zero
+ * on entry: only the rows the batch touches are written, a row that occurs in several slots as the sum of its slots in
+ * slot order, plus l2_emb item on every row when l2_emb != 0).  A batch without any target yields gradients of exactly
+ * zero and a loss term of zero.
+ * Work buffers: d_keys uint64 [3 batch L]; d_ws float [nrhip_sasrec_workspace_floats].
+ * Limits: hidden_units 1..NRHIP_SASREC_MAX_WIDTH, max_len 1..NRHIP_SASREC_MAX_LEN, blocks 1..NRHIP_SASREC_MAX_BLOCKS,
+ * batch 0..NRHIP_SASREC_MAX_BATCH, num_heads * batch * max_len^2 <= NRHIP_SASREC_MAX_WEIGHTS (the saved attention
+ * weights); outside: NRHIP_ERR_UNSUPPORTED.  num_heads must divide hidden_units (NRHIP_ERR_ARG).  batch == 0 launches
+ * nothing and writes nothing.  fp32 throughout (the two reported sums are added in double and rounded once), every sum
+ * in a fixed order, no atomics: two calls on the same inputs are bit-identical. */
+#define NRHIP_SASREC_MAX_BLOCKS 4
+#define NRHIP_SASREC_MAX_WIDTH 128
+#define NRHIP_SASREC_MAX_LEN 200
+#define NRHIP_SASREC_MAX_BATCH 4096
+#define NRHIP_SASREC_BLOCK_VARS 14
+#define NRHIP_SASREC_MAX_SITES (1 + 3 * NRHIP_SASREC_MAX_BLOCKS)
+#define NRHIP_SASREC_MAX_WEIGHTS (1ll << 30)
+typedef struct nrhip_sasrec_weights {
+  const float* d_item;
+  const float* d_pos;
+  const float* d_blk[NRHIP_SASREC_MAX_BLOCKS][NRHIP_SASREC_BLOCK_VARS];
+  const float* d_lnf_beta;
+  const float* d_lnf_gamma;
+  int n_items, d, L, n_blocks, n_heads;
+} nrhip_sasrec_weights;
+typedef struct nrhip_sasrec_step_args {
+  nrhip_sasrec_weights w;
+  float* d_G_item;
+  float* d_G_pos;
+  float* d_G_blk[NRHIP_SASREC_MAX_BLOCKS][NRHIP_SASREC_BLOCK_VARS];
+  float* d_G_lnf_beta;
+  float* d_G_lnf_gamma;
+  const int32_t* d_seq;
+  const int32_t* d_pos_ids;
+  const int32_t* d_neg_ids;
+  const uint8_t* d_mask[NRHIP_SASREC_MAX_SITES];
+  uint64_t* d_keys;
+  float* d_ws;
+  float* d_loss2;
+  uint64_t seed;
+  int batch, step;
+  float rate, l2_emb;
+} nrhip_sasrec_step_args;
+/* Replaces the storage TensorFlow gives the intermediate tensors of the graph and their gradients: the size in floats
+ * of d_ws for batches up to max_batch (nrhip_sasrec_forward needs no more). */
+int nrhip_sasrec_workspace_floats(int max_batch, int max_len, int hidden_units, int num_blocks, int num_heads,
+                                  size_t* floats);
+/* Replaces one `sess.run(self.train_opt, feed_dict=feed)` of SASRec.py:402 up to the optimiser; the head of this section
+ * has the graph, the outputs and the limits. */
+int nrhip_sasrec_step(const nrhip_sasrec_step_args* args, void* stream);
+/* Replaces the forward half of `sess.run(self.all_logits, ...)` of SASRec.py:438: the graph with training off on d_seq
+ * [batch][L]; d_out[b][0..d) = scale * z[b][L - 1] (row stride ld).  An all-padded row gives lnf's beta. */
+int nrhip_sasrec_forward(const nrhip_sasrec_weights* weights, const int32_t* d_seq, int batch, float* d_ws, float scale,
+                         float* d_out, int64_t ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

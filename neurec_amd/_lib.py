@@ -254,6 +254,26 @@ class Gru4recplusStepArgs(C.Structure):
         [("reg", C.c_float), ("bpr_reg", C.c_float)]
 
 
+SASREC_MAX_BLOCKS, SASREC_BLOCK_VARS = 4, 14
+SASREC_MAX_SITES = 1 + 3 * SASREC_MAX_BLOCKS
+
+
+class SasrecWeights(C.Structure):
+    """nrhip_sasrec_weights (include/neurec_hip.h)"""
+    _fields_ = [("item", C.c_void_p), ("pos", C.c_void_p), ("blk", (C.c_void_p * SASREC_BLOCK_VARS) * SASREC_MAX_BLOCKS),
+                ("lnf_beta", C.c_void_p), ("lnf_gamma", C.c_void_p)] + \
+        [(n, C.c_int) for n in ("n_items", "d", "L", "n_blocks", "n_heads")]
+
+
+class SasrecStepArgs(C.Structure):
+    """nrhip_sasrec_step_args (include/neurec_hip.h)"""
+    _fields_ = [("w", SasrecWeights), ("G_item", C.c_void_p), ("G_pos", C.c_void_p),
+                ("G_blk", (C.c_void_p * SASREC_BLOCK_VARS) * SASREC_MAX_BLOCKS), ("G_lnf_beta", C.c_void_p),
+                ("G_lnf_gamma", C.c_void_p), ("seq", C.c_void_p), ("pos_ids", C.c_void_p), ("neg_ids", C.c_void_p),
+                ("mask", C.c_void_p * SASREC_MAX_SITES), ("keys", C.c_void_p), ("ws", C.c_void_p), ("loss2", C.c_void_p),
+                ("seed", C.c_uint64), ("batch", C.c_int), ("step", C.c_int), ("rate", C.c_float), ("l2_emb", C.c_float)]
+
+
 # name -> argtypes; every function returns int status except where noted.
 SIGNATURES = {
     "nrhip_device_info": [C.POINTER(i32), C.POINTER(i32), psz, C.c_char_p, i32],
@@ -466,6 +486,9 @@ SIGNATURES = {
     "nrhip_gru4rec_scores": [p, i64, p, p, i32, i32, i32, i32, p, i64, p],
     "nrhip_gru4recplus_workspace_floats": [i32, C.POINTER(i32), i32, i32, psz],
     "nrhip_gru4recplus_step": [C.POINTER(Gru4recplusStepArgs), p],
+    "nrhip_sasrec_workspace_floats": [i32, i32, i32, i32, i32, psz],
+    "nrhip_sasrec_step": [C.POINTER(SasrecStepArgs), p],
+    "nrhip_sasrec_forward": [C.POINTER(SasrecWeights), p, i32, p, C.c_float, p, i64, p],
 }
 
 for _name, _args in SIGNATURES.items():

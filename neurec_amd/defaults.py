@@ -58,6 +58,8 @@ MODELS = {
     "GRU4RecPlus": [("lr", "0.01"), ("reg", "0.0"), ("bpr_reg", "1.0"), ("layers", "[100]"), ("batch_size", "256"),
                     ("loss", "bpr_max"), ("hidden_act", "tanh"), ("final_act", "linear"), ("n_sample", "2048"),
                     ("sample_alpha", "0.75"), ("epochs", "1000")],
+    "SASRec": [("lr", "0.001"), ("l2_emb", "0.0"), ("hidden_units", "50"), ("dropout_rate", "0.5"), ("max_len", "50"),
+               ("num_blocks", "2"), ("num_heads", "1"), ("batch_size", "128"), ("epochs", "1000")],
 }
 
 
