@@ -15,13 +15,12 @@ d + 1 with s_u over a [U, L] table of the users' last items.
 """
 import ctypes as C
 
-import numpy as np
 import torch
 
-from . import engine as E
 from ._lib import FossilStepArgs, call
 from .engine import _ptr, _stream
-from .history import HistoryEngine, _addr, _f32
+from .history import HistoryEngine
+from .row_learner import ScoreCache, addr, as_ids, f32
 
 MAX_D = 128                   # NRHIP_FOSSIL_MAX_D
 MAX_ORDER = 16                # NRHIP_FOSSIL_MAX_ORDER
@@ -38,7 +37,7 @@ class FossilEngine(HistoryEngine):
 
     def __init__(self, c1, Q, eta, eta_bias, train, lr, regs, alpha, max_batch, loss="bpr", pairwise=True,
                  learner="adagrad", bias=None, momentum=0.9, last_items=None):
-        eta = _f32(eta)
+        eta = f32(eta)
         if eta.dim() != 2:
             raise ValueError("eta must be [num_users, high_order]")
         U, L = eta.shape
@@ -48,7 +47,7 @@ class FossilEngine(HistoryEngine):
             raise ValueError("regs holds three entries: the pooled history's, the embeddings' and eta's")
 
         def dense(d):
-            eb = _f32(eta_bias).reshape(-1)
+            eb = f32(eta_bias).reshape(-1)
             if eb.numel() != L:
                 raise ValueError("eta_bias must hold high_order entries")
             return {"eta_bias": eb}
@@ -61,10 +60,8 @@ class FossilEngine(HistoryEngine):
         self.L, self.reg_eta = L, float(regs[2])
         self.eta = eta.contiguous().to(dev)
         self.G["eta"] = torch.zeros_like(self.eta)
-        init = {"adam": 0.0, "gd": None, "adagrad": 1e-8, "rmsprop": 1.0, "momentum": 0.0}[self.learner]
-        self.s0["eta"] = None if init is None else torch.full_like(self.eta, init)
-        self.s1["eta"] = torch.zeros_like(self.eta) if self.learner in ("adam", "rmsprop") else None
-        self.flag_eta = None if self.flag_Q is None else torch.zeros(max(U, 1), dtype=torch.uint8, device=dev)
+        self.s0["eta"], self.s1["eta"] = self.opt.slots(self.eta)
+        self.flag_eta = self.opt.flag(max(U, 1), dev)
         self._g = torch.empty((N, d), dtype=torch.float32, device=dev)
         self._x = torch.empty((N, d), dtype=torch.float32, device=dev)
         self._dots = torch.empty((N, L), dtype=torch.float32, device=dev)
@@ -72,28 +69,20 @@ class FossilEngine(HistoryEngine):
         self._nothing = {t: torch.zeros(L, dtype=t, device=dev) for t in (torch.int32, torch.float32)}
         self.last_items = None if last_items is None else self._last(last_items)   # score()'s default
         self._factors = None                                   # (step, last_items, users' factors, items' factors)
-        self._gemm = None
+        self._scores = ScoreCache()
 
     def _field(self, t, dtype):
         # an empty batch is a step too (eta_bias's regulariser enters once per step): the C call wants an address
         return _ptr(t if t.numel() else self._nothing[dtype], dtype)
 
     def _fill(self, a):
-        a.eta, a.G_eta, a.flag_eta = _ptr(self.eta), _ptr(self.G["eta"]), _addr(self.flag_eta)
+        a.eta, a.G_eta, a.flag_eta = _ptr(self.eta), _ptr(self.G["eta"]), addr(self.flag_eta)
         a.recents = self._field(self._recents, torch.int32)
         a.g, a.x, a.dots = _ptr(self._g), _ptr(self._x), _ptr(self._dots)
         a.L, a.reg_eta = self.L, self.reg_eta
 
     def _apply_more(self):
-        var, grad, s0, s1 = self.eta, self.G["eta"], self.s0["eta"], self.s1["eta"]
-        if self.learner == "adam":
-            E.adam_sparse(var, s0, s1, grad, self.adam)
-        elif self.learner == "rmsprop":
-            E.optimizer_rows("rmsprop", var, s0, s1, grad, self.flag_eta, self.lr, 0.9, 0.0, 1e-10)
-        elif self.learner == "momentum":
-            E.optimizer_rows("momentum", var, s0, None, grad, self.flag_eta, self.lr, self.momentum)
-        else:
-            E.optimizer_rows(self.learner, var, s0, None, grad, self.flag_eta, self.lr)
+        self.opt.apply(self.eta, self.s0["eta"], self.s1["eta"], self.G["eta"], self.flag_eta)
 
     def gradients(self, users, recents, items, third, loss_out):
         """the C call alone: loss_out and the gradient buffers self.G (and the row flags); no table moves"""
@@ -117,14 +106,8 @@ class FossilEngine(HistoryEngine):
 
     # ------------------------------------------------------------------ scoring
     def _last(self, last_items):
-        dev = self.c1.device
-        if not isinstance(last_items, torch.Tensor):
-            last_items = torch.from_numpy(np.ascontiguousarray(last_items, dtype=np.int32))
-        last_items = last_items.to(dev, torch.int32).contiguous()
-        if last_items.numel() != self.n_users * self.L:
-            raise ValueError("last_items holds %d entries, not [num_users, high_order] = [%d, %d]" %
-                             (last_items.numel(), self.n_users, self.L))
-        return last_items
+        return as_ids(last_items, self.c1.device, self.n_users * self.L,
+                      "last_items holds {n} entries, not [num_users, high_order] = [%d, %d]" % (self.n_users, self.L))
 
     def user_factors(self, last_items, users=None):
         """[B, d + 1] rows [ |R_u|^-alpha p_u + sum_l w_{u,l} c1[last_items[u, l]] | 1 ] of `users` (int32 device
@@ -151,19 +134,9 @@ class FossilEngine(HistoryEngine):
     def score(self, users, last_items=None):
         """S [B, I] float32 on the device: Fossil.py:177-217 for `users`, every item, own items included; last_items
         None: the table the engine was built with"""
-        dev = self.c1.device
         if last_items is None:
             if self.last_items is None:
                 raise ValueError("score() needs the [num_users, high_order] table of last items")
             last_items = self.last_items
-        if not isinstance(users, torch.Tensor):
-            users = torch.from_numpy(np.ascontiguousarray(users, dtype=np.int32))
-        users = users.to(dev, torch.int32).contiguous()
-        B = int(users.numel())
-        P = self.user_factors(self._last(last_items), users)
-        Q = self.item_factors()
-        if self._gemm is None or self._gemm.max_rows < B:
-            self._gemm = E.score_gemm_for(Q, max(B, 1))
-        else:
-            self._gemm.prepare(Q)
-        return self._gemm(P, None)[:, :self.n_items]
+        P = self.user_factors(self._last(last_items), as_ids(users, self.c1.device))
+        return self._scores.score(P, self.item_factors(), self.n_items)

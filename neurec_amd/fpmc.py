@@ -2,32 +2,23 @@
 `sess.run((loss, optimizer))` per step (csrc/fpmc.hip).
 
 An instance is (user, recent item, item[, negative]) and its score x(u, l, i) = <UI[u], IU[i]> + <IL[i], LI[l]>.  All
-four tables are read through embedding_lookup only, so TF-1.12 gives every one the sparse application: Adam's sparse
-form (every row swept), the row kernels for gd / adagrad / rmsprop / momentum — what GeneralMFEngine does for MF and
-HistoryEngine for `embedding_Q`.
+four tables are read through embedding_lookup only, so TF-1.12 gives every one the sparse application
+(neurec_amd/row_learner.py).
 
 The score has a factor form, x(u, l, i) = [UI[u] | LI[l]] . [IU[i] | IL[i]]: evaluation is the factor path at width
 2 d with l = the user's most recent train item.
 """
 import ctypes as C
 
-import numpy as np
 import torch
 
 from . import engine as E
 from ._lib import FpmcStepArgs, call
 from .engine import _ptr, _stream
+from .row_learner import RowLearner, ScoreCache, addr, as_ids, check_loss_learner, f32
 
 MAX_D = 128                   # NRHIP_FPMC_MAX_D
 _TABLES = ("UI", "IU", "IL", "LI")
-
-
-def _addr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _f32(x):
-    return torch.as_tensor(np.asarray(x), dtype=torch.float32)
 
 
 class FPMCEngine:
@@ -39,13 +30,8 @@ class FPMCEngine:
 
     def __init__(self, UI, IU, IL, LI, lr, reg_mf, max_batch, loss="cross_entropy", pairwise=False, learner="adam",
                  momentum=0.9):
-        loss, learner = str(loss).lower(), str(learner).lower()
-        table = E.PAIRWISE_LOSSES if pairwise else E.POINTWISE_LOSSES
-        if loss not in table:
-            raise Exception("please choose a suitable loss function")        # learner.py:28,40
-        if learner != "adam" and learner not in E.ROW_OPTIMIZERS:
-            raise ValueError("please select a suitable optimizer")           # learner.py:15
-        UI, IU, IL, LI = _f32(UI), _f32(IU), _f32(IL), _f32(LI)
+        loss, learner, self.loss_kind = check_loss_learner(loss, learner, pairwise)
+        UI, IU, IL, LI = f32(UI), f32(IU), f32(IL), f32(LI)
         if UI.dim() != 2 or IU.dim() != 2 or IU.shape[1] != UI.shape[1] or \
                 tuple(IL.shape) != tuple(IU.shape) or tuple(LI.shape) != tuple(IU.shape):
             raise ValueError("UI must be [num_users, embedding_size], IU / IL / LI [num_items, embedding_size]")
@@ -54,38 +40,22 @@ class FPMCEngine:
             raise NotImplementedError("FPMC: embedding_size=%d is not supported (1 to %d)" % (d, MAX_D))
         dev = E.require_gpu()
         self.loss, self.pairwise, self.learner = loss, bool(pairwise), learner
-        self.loss_kind = table[loss]
         self.n_users, self.n_items, self.d = U, I, d
         self.UI, self.IU, self.IL, self.LI = (t.contiguous().to(dev) for t in (UI, IU, IL, LI))
         self.G = {k: torch.zeros_like(getattr(self, k)) for k in _TABLES}
         self.lr, self.momentum, self.reg_mf = float(lr), float(momentum), float(reg_mf)
         self.adam = E.AdamState(lr)
-        init = {"adam": 0.0, "gd": None, "adagrad": 1e-8, "rmsprop": 1.0, "momentum": 0.0}[learner]
-        two = learner in ("adam", "rmsprop")
-        mk = lambda t, v: None if v is None else torch.full_like(t, v)
-        self.s0 = {k: mk(getattr(self, k), init) for k in _TABLES}
-        self.s1 = {k: (mk(getattr(self, k), 0.0) if two else None) for k in _TABLES}
-        rows = learner != "adam"
-        self.flag = {k: (torch.zeros(getattr(self, k).shape[0], dtype=torch.uint8, device=dev) if rows else None)
-                     for k in _TABLES}
+        self.opt = RowLearner(learner, lr, momentum, self.adam)
+        slots = {k: self.opt.slots(getattr(self, k)) for k in _TABLES}
+        self.s0, self.s1 = ({k: s[i] for k, s in slots.items()} for i in (0, 1))
+        self.flag = {k: self.opt.flag(getattr(self, k).shape[0], dev) for k in _TABLES}
         self.max_batch = int(max_batch)
         N = max(self.max_batch, 1) * (2 if self.pairwise else 1)
         self._keys = torch.empty(3 * N, dtype=torch.int64, device=dev)
         self._scal = torch.empty(4 * max(self.max_batch, 1), dtype=torch.float32, device=dev)
         self.t = 0
         self._factors = None                                   # (step, last_items, P', Q')
-        self._gemm = None
-
-    def _apply_rows(self, key):
-        var, grad, s0, s1, flag = getattr(self, key), self.G[key], self.s0[key], self.s1[key], self.flag[key]
-        if self.learner == "adam":
-            E.adam_sparse(var, s0, s1, grad, self.adam)
-        elif self.learner == "rmsprop":
-            E.optimizer_rows("rmsprop", var, s0, s1, grad, flag, self.lr, 0.9, 0.0, 1e-10)
-        elif self.learner == "momentum":
-            E.optimizer_rows("momentum", var, s0, None, grad, flag, self.lr, self.momentum)
-        else:
-            E.optimizer_rows(self.learner, var, s0, None, grad, flag, self.lr)
+        self._scores = ScoreCache()
 
     def gradients(self, users, recent, items, third, loss_out):
         """the C call alone: loss_out and the batch's rows of self.G (and the row flags); no table moves"""
@@ -98,7 +68,7 @@ class FPMCEngine:
         for k in _TABLES:
             setattr(a, k, _ptr(getattr(self, k)))
             setattr(a, "G_" + k, _ptr(self.G[k]))
-            setattr(a, "flag_" + k, _addr(self.flag[k]))
+            setattr(a, "flag_" + k, addr(self.flag[k]))
         a.users, a.recent, a.items = _ptr(users, torch.int32), _ptr(recent, torch.int32), _ptr(items, torch.int32)
         a.third = _ptr(third, torch.int32 if self.pairwise else torch.float32)
         a.keys, a.scal, a.loss2 = _ptr(self._keys), _ptr(self._scal), _ptr(loss_out, torch.float32)
@@ -109,7 +79,7 @@ class FPMCEngine:
     def apply(self):
         """the four applications of self.G; the gradient rows (and flags) are zero again afterwards"""
         for k in _TABLES:
-            self._apply_rows(k)
+            self.opt.apply(getattr(self, k), self.s0[k], self.s1[k], self.G[k], self.flag[k])
         self.adam.advance()
         self.t += 1
 
@@ -121,13 +91,8 @@ class FPMCEngine:
 
     # ------------------------------------------------------------------ scoring
     def _last(self, last_items):
-        dev = self.UI.device
-        if not isinstance(last_items, torch.Tensor):
-            last_items = torch.from_numpy(np.ascontiguousarray(last_items, dtype=np.int32))
-        last_items = last_items.to(dev, torch.int32).contiguous()
-        if last_items.numel() != self.n_users:
-            raise ValueError("last_items holds %d entries, the user table %d rows" % (last_items.numel(), self.n_users))
-        return last_items
+        return as_ids(last_items, self.UI.device, self.n_users,
+                      "last_items holds {n} entries, the user table {want} rows")
 
     def user_factors(self, last_items, users=None):
         """[n, 2 d] rows [UI[u] | LI[last_items[u]]] of `users` (int32 device tensor; None: every user); last -1: the
@@ -158,15 +123,5 @@ class FPMCEngine:
 
     def score(self, users, last_items):
         """S [n, I] float32 on the device: FPMC.py:140-152 for `users`, every item, own items included"""
-        dev = self.UI.device
-        if not isinstance(users, torch.Tensor):
-            users = torch.from_numpy(np.ascontiguousarray(users, dtype=np.int32))
-        users = users.to(dev, torch.int32).contiguous()
-        n = int(users.numel())
-        P = self.user_factors(self._last(last_items), users)
-        Q = self.item_factors()
-        if self._gemm is None or self._gemm.max_rows < n:
-            self._gemm = E.score_gemm_for(Q, max(n, 1))
-        else:
-            self._gemm.prepare(Q)
-        return self._gemm(P, None)[:, :self.n_items]
+        P = self.user_factors(self._last(last_items), as_ids(users, self.UI.device))
+        return self._scores.score(P, self.item_factors(), self.n_items)

@@ -7,16 +7,17 @@ b [1, w], h [w, 1]) that weights the L recents per target item:
 The attention depends on the target item, so the score has no factor form: evaluation has a kernel of its own, as NAIS.
 
 Optimiser forms, as TF-1.12 picks them: the four tables are read through embedding_lookup only — the sparse
-application, exactly FPMCEngine._apply_rows; W, b and h are read through matmul — the dense Apply* kernels, every step.
+application (neurec_amd/row_learner.py); W, b and h are read through matmul — the dense Apply* kernels, every step.
 """
 import ctypes as C
 
-import numpy as np
 import torch
 
 from . import engine as E
 from ._lib import FpmcplusScoresArgs, FpmcplusStepArgs, call
 from .engine import _ptr, _stream
+from .model._common import last_items_table            # noqa: F401  (predict()'s table, made by the plugin)
+from .row_learner import RowLearner, addr, as_ids, check_loss_learner, f32
 
 MAX_D = 128                   # NRHIP_FPMCPLUS_MAX_D
 MAX_W = 64                    # NRHIP_FPMCPLUS_MAX_W
@@ -25,27 +26,6 @@ MAX_CHUNKS = 64               # NRHIP_FPMCPLUS_MAX_CHUNKS
 _ROWS = ("UI", "IU", "IL", "LI")
 _DENSE = ("W", "b", "h")
 _TABLES = _ROWS + _DENSE
-
-
-def _addr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _f32(x):
-    return torch.as_tensor(np.asarray(x), dtype=torch.float32)
-
-
-def last_items_table(train_dict, n_users, high_order):
-    """[n_users, L] int32: row u = the user's last min(|R_u|, L) train items by time, oldest first, padded with -1 —
-    the attention of predict() runs over exactly these (a user with fewer than L items: the softmax covers the items
-    there are; none: the row is all -1)"""
-    L = int(high_order)
-    out = np.full((int(n_users), L), -1, np.int32)
-    for u, seq in train_dict.items():
-        tail = list(seq)[-L:]
-        if tail:
-            out[int(u), :len(tail)] = tail
-    return out
 
 
 class FPMCplusEngine:
@@ -57,13 +37,8 @@ class FPMCplusEngine:
 
     def __init__(self, UI, IU, IL, LI, W, b, h, lr, reg_mf, reg_w, max_batch, high_order, loss="bpr", pairwise=True,
                  learner="adam", momentum=0.9, last_items=None):
-        loss, learner = str(loss).lower(), str(learner).lower()
-        table = E.PAIRWISE_LOSSES if pairwise else E.POINTWISE_LOSSES
-        if loss not in table:
-            raise Exception("please choose a suitable loss function")        # learner.py:28,40
-        if learner != "adam" and learner not in E.ROW_OPTIMIZERS:
-            raise ValueError("please select a suitable optimizer")           # learner.py:15
-        UI, IU, IL, LI, W = _f32(UI), _f32(IU), _f32(IL), _f32(LI), _f32(W)
+        loss, learner, self.loss_kind = check_loss_learner(loss, learner, pairwise)
+        UI, IU, IL, LI, W = f32(UI), f32(IU), f32(IL), f32(LI), f32(W)
         if UI.dim() != 2 or IU.dim() != 2 or IU.shape[1] != UI.shape[1] or \
                 tuple(IL.shape) != tuple(IU.shape) or tuple(LI.shape) != tuple(IU.shape):
             raise ValueError("UI must be [num_users, embedding_size], IU / IL / LI [num_items, embedding_size]")
@@ -75,7 +50,7 @@ class FPMCplusEngine:
         w = int(W.shape[1])
         if w < 1 or w > MAX_W:
             raise NotImplementedError("FPMCplus: weight_size=%d is not supported (1 to %d)" % (w, MAX_W))
-        b, h = _f32(b).reshape(-1), _f32(h).reshape(-1)
+        b, h = f32(b).reshape(-1), f32(h).reshape(-1)
         if b.numel() != w or h.numel() != w:
             raise ValueError("b and h must hold weight_size entries")
         L = int(high_order)
@@ -83,7 +58,6 @@ class FPMCplusEngine:
             raise NotImplementedError("FPMCplus: high_order=%d is not supported (1 to %d)" % (L, MAX_L))
         dev = E.require_gpu()
         self.loss, self.pairwise, self.learner = loss, bool(pairwise), learner
-        self.loss_kind = table[loss]
         self.n_users, self.n_items, self.d, self.w, self.L = U, I, d, w, L
         self.UI, self.IU, self.IL, self.LI, self.W, self.b, self.h = \
             (t.contiguous().to(dev) for t in (UI, IU, IL, LI, W, b, h))
@@ -91,17 +65,11 @@ class FPMCplusEngine:
         self.lr, self.momentum = float(lr), float(momentum)
         self.reg_mf, self.reg_w = float(reg_mf), float(reg_w)
         self.adam = E.AdamState(lr)
-        self.dense = E.make_learner(learner, lr)               # W, b, h; None: ApplyAdam
-        if self.dense is not None:
-            self.dense.momentum = self.momentum
-        init = {"adam": 0.0, "gd": None, "adagrad": 1e-8, "rmsprop": 1.0, "momentum": 0.0}[learner]
-        two = learner in ("adam", "rmsprop")
-        mk = lambda t, v: None if v is None else torch.full_like(t, v)
-        self.s0 = {k: mk(getattr(self, k), init) for k in _TABLES}
-        self.s1 = {k: (mk(getattr(self, k), 0.0) if two else None) for k in _TABLES}
-        rows = learner != "adam"
-        self.flag = {k: (torch.zeros(getattr(self, k).shape[0], dtype=torch.uint8, device=dev) if rows else None)
-                     for k in _ROWS}
+        self.opt = RowLearner(learner, lr, momentum, self.adam)
+        self.dense = self.opt.dense                           # W, b, h; None: ApplyAdam
+        slots = {k: self.opt.slots(getattr(self, k)) for k in _TABLES}
+        self.s0, self.s1 = ({k: s[i] for k, s in slots.items()} for i in (0, 1))
+        self.flag = {k: self.opt.flag(getattr(self, k).shape[0], dev) for k in _ROWS}
         self.max_batch = int(max_batch)
         mb = max(self.max_batch, 1)
         K = (5 if self.pairwise else 3) + L                    # looked-up rows per instance
@@ -119,33 +87,13 @@ class FPMCplusEngine:
 
     def set_last_items(self, last_items):
         """the [U, L] table of predict(): the user's last min(|R_u|, L) items, -1 where there is none"""
-        if not isinstance(last_items, torch.Tensor):
-            last_items = torch.from_numpy(np.ascontiguousarray(last_items, dtype=np.int32))
-        last_items = last_items.to(self.UI.device, torch.int32).contiguous()
+        last_items = as_ids(last_items, self.UI.device)
         if tuple(last_items.shape) != (self.n_users, self.L):
             raise ValueError("last items must be [num_users, high_order] = [%d, %d], got %s"
                              % (self.n_users, self.L, tuple(last_items.shape)))
         self.last_items = last_items
 
     # ------------------------------------------------------------------ training
-    def _apply_rows(self, key):
-        var, grad, s0, s1, flag = getattr(self, key), self.G[key], self.s0[key], self.s1[key], self.flag[key]
-        if self.learner == "adam":
-            E.adam_sparse(var, s0, s1, grad, self.adam)
-        elif self.learner == "rmsprop":
-            E.optimizer_rows("rmsprop", var, s0, s1, grad, flag, self.lr, 0.9, 0.0, 1e-10)
-        elif self.learner == "momentum":
-            E.optimizer_rows("momentum", var, s0, None, grad, flag, self.lr, self.momentum)
-        else:
-            E.optimizer_rows(self.learner, var, s0, None, grad, flag, self.lr)
-
-    def _apply_dense(self):
-        if self.dense is None:
-            for k in _DENSE:
-                E.adam_dense(getattr(self, k), self.s0[k], self.s1[k], self.G[k], self.adam, clear_grad=True)
-        else:
-            self.dense.apply([(getattr(self, k), self.s0[k], self.s1[k], self.G[k], True) for k in _DENSE])
-
     def gradients(self, users, recents, items, third, loss_out):
         """the C call alone: loss_out, the batch's rows of self.G (and the row flags) and G_W / G_b / G_h whole; no
         table moves.  An empty batch is no work: nothing is launched and loss_out is set to zero."""
@@ -165,7 +113,7 @@ class FPMCplusEngine:
             setattr(a, k, _ptr(getattr(self, k)))
             setattr(a, "G_" + k, _ptr(self.G[k]))
         for k in _ROWS:
-            setattr(a, "flag_" + k, _addr(self.flag[k]))
+            setattr(a, "flag_" + k, addr(self.flag[k]))
         a.users, a.recents, a.items = _ptr(users, torch.int32), _ptr(recents, torch.int32), _ptr(items, torch.int32)
         a.third = _ptr(third, torch.int32 if self.pairwise else torch.float32)
         a.keys, a.contrib, a.scal = _ptr(self._keys), _ptr(self._contrib), _ptr(self._scal)
@@ -177,8 +125,8 @@ class FPMCplusEngine:
     def apply(self):
         """the seven applications of self.G; the gradient buffers (and flags) are zero again afterwards"""
         for k in _ROWS:
-            self._apply_rows(k)
-        self._apply_dense()
+            self.opt.apply(getattr(self, k), self.s0[k], self.s1[k], self.G[k], self.flag[k])
+        self.opt.apply_dense([(getattr(self, k), self.s0[k], self.s1[k], self.G[k]) for k in _DENSE], clear_grad=True)
         self.adam.advance()
         self.t += 1
 
@@ -196,9 +144,7 @@ class FPMCplusEngine:
         if self.last_items is None:
             raise ValueError("score() needs the last items table: pass last_items= or call set_last_items()")
         dev = self.UI.device
-        if not isinstance(users, torch.Tensor):
-            users = torch.from_numpy(np.ascontiguousarray(users, dtype=np.int32))
-        users = users.to(dev, torch.int32).contiguous()
+        users = as_ids(users, dev)
         n, I = int(users.numel()), self.n_items
         out = torch.empty((n, I), dtype=torch.float32, device=dev)
         if n == 0 or I == 0:

@@ -17,6 +17,7 @@ import torch
 from . import engine as E
 from ._lib import Gru4recStepArgs, Gru4recWeights, call
 from .engine import _ptr, _stream
+from .row_learner import as_ids, f32
 
 MAX_LAYERS = 3                # NRHIP_GRU4REC_MAX_LAYERS
 MAX_WIDTH = 128               # NRHIP_GRU4REC_MAX_WIDTH
@@ -27,10 +28,6 @@ FINAL_ACTS = {"linear": 0, "relu": 1, "leaky_relu": 2}
 LOSSES = {"top1": 0, "bpr": 1}
 _ROWS = ("E_in", "Q", "b")
 _CELL = ("Wg", "bg", "Wc", "bc")
-
-
-def _f32(x):
-    return torch.as_tensor(np.asarray(x), dtype=torch.float32)
 
 
 class GRU4RecEngine:
@@ -47,10 +44,10 @@ class GRU4RecEngine:
             raise ValueError("There is not final_act named '%s'." % final_act)         # GRU4Rec.py:44
         if loss not in LOSSES:
             raise ValueError("There is not loss named '%s'." % loss)                   # GRU4Rec.py:51
-        cells = [tuple(_f32(t) for t in c) for c in cells]
+        cells = [tuple(f32(t) for t in c) for c in cells]
         if not 1 <= len(cells) <= MAX_LAYERS:
             raise NotImplementedError("GRU4Rec: %d layers are not supported (1 to %d)" % (len(cells), MAX_LAYERS))
-        E_in, Q, b = _f32(E_in), _f32(Q), _f32(b).reshape(-1)
+        E_in, Q, b = f32(E_in), f32(Q), f32(b).reshape(-1)
         if E_in.dim() != 2 or Q.dim() != 2 or Q.shape[0] != E_in.shape[0] or b.numel() != E_in.shape[0]:
             raise ValueError("E_in must be [num_items, layers[0]], Q [num_items, layers[-1]], b [num_items]")
         layers = [int(c[1].numel()) // 2 for c in cells]
@@ -189,7 +186,7 @@ class GRU4RecEngine:
                 raise ValueError("GRU4Rec: %s holds an item outside [0, %d)" % (name, self.n_items))
         dev = self.E_in.device
         up = lambda a: a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
-        X, Y = up(X).to(dev, torch.int32).contiguous(), up(Y).to(dev, torch.int32).contiguous()
+        X, Y = as_ids(X, dev), as_ids(Y, dev)
         reset = up(reset).to(dev, torch.uint8).contiguous()
         if X.dim() != 2 or X.shape != Y.shape or X.shape != reset.shape or losses.shape[0] < X.shape[0]:
             raise ValueError("X, Y and reset must be [steps, batch], losses [steps, 2]")

@@ -15,6 +15,7 @@ import torch
 
 from ._lib import Gru4recplusStepArgs, call
 from .engine import _ptr, _stream
+from .row_learner import as_ids
 from .gru4rec import _CELL, FINAL_ACTS, HIDDEN_ACTS, MAX_BATCH, GRU4RecEngine
 
 MAX_SAMPLE = 8192             # NRHIP_GRU4RECPLUS_MAX_SAMPLE
@@ -83,7 +84,7 @@ class GRU4RecPlusEngine(GRU4RecEngine):
                 raise ValueError("GRU4RecPlus: %s holds an item outside [0, %d)" % (name, self.n_items))
         dev = self.E_in.device
         up = lambda a: a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
-        X, Y = up(X).to(dev, torch.int32).contiguous(), up(Y).to(dev, torch.int32).contiguous()
+        X, Y = as_ids(X, dev), as_ids(Y, dev)
         reset = up(reset).to(dev, torch.uint8).contiguous()
         if X.dim() != 2 or Y.dim() != 2 or Y.shape[0] != X.shape[0] or Y.shape[1] != X.shape[1] + self.n_sample or \
                 X.shape != reset.shape or losses.shape[0] < X.shape[0]:

@@ -5,7 +5,7 @@ A user is not a table row but a pooling of the `c1` rows of the train history; a
 item or none, count).  Both engines hold c1 / Q / bias, the train matrix and its transpose, one optimiser state per
 table, the instance buffers of a batch, and run one C call per step followed by the same applications: `c1` and the
 model's dense variables through the dense Apply* kernels (or c1 by rows, `c1_application="rows"`), `embedding_Q` and
-`bias` by rows — the forms TF-1.12 picks for tf.concat reads and embedding_lookup reads.
+`bias` by rows — the forms TF-1.12 picks for tf.concat reads and embedding_lookup reads (neurec_amd/row_learner.py).
 """
 import ctypes as C
 
@@ -16,14 +16,7 @@ import torch
 from . import engine as E
 from ._lib import call
 from .engine import _ptr, _stream
-
-
-def _addr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _f32(x):
-    return torch.as_tensor(np.asarray(x), dtype=torch.float32)
+from .row_learner import RowLearner, addr, check_loss_learner, f32
 
 
 class HistoryEngine:
@@ -35,15 +28,10 @@ class HistoryEngine:
                  c1_application, dense=None, sorted_rows=False):
         """dense(d): the model's further variables {name: float32 tensor}, checked against embedding_size d — dense
         variables to TF; sorted_rows: de-duplicate the train rows and sort their columns"""
-        loss, learner = str(loss).lower(), str(learner).lower()
-        table = E.PAIRWISE_LOSSES if pairwise else E.POINTWISE_LOSSES
-        if loss not in table:
-            raise Exception("please choose a suitable loss function")        # learner.py:28,40
-        if learner != "adam" and learner not in E.ROW_OPTIMIZERS:
-            raise ValueError("please select a suitable optimizer")           # learner.py:15
+        loss, learner, self.loss_kind = check_loss_learner(loss, learner, pairwise)
         if c1_application not in ("dense", "rows"):
             raise ValueError("c1_application is 'dense' or 'rows', got %r" % (c1_application,))
-        c1, Q = _f32(c1), _f32(Q)
+        c1, Q = f32(c1), f32(Q)
         if c1.dim() != 2 or tuple(c1.shape) != tuple(Q.shape):
             raise ValueError("c1 and embedding_Q must both be [num_items, embedding_size]")
         I, d = c1.shape
@@ -58,13 +46,12 @@ class HistoryEngine:
             M.sort_indices()
         dev = E.require_gpu()
         self.loss, self.pairwise, self.learner = loss, bool(pairwise), learner
-        self.loss_kind = table[loss]
         self.n_users, self.n_items, self.d = M.shape[0], I, d
         self.csr = E.DeviceCSR.from_scipy(M)
         self.csc = E.DeviceCSR.from_scipy(M.T)                 # item -> its users, ascending
         self.h_deg = np.diff(np.asarray(M.indptr, dtype=np.int64))
         self.c1, self.Q = c1.contiguous().to(dev), Q.contiguous().to(dev)
-        self.bias = (torch.zeros(I) if bias is None else _f32(bias)).contiguous().to(dev)
+        self.bias = (torch.zeros(I) if bias is None else f32(bias)).contiguous().to(dev)
         for k, t in more.items():
             setattr(self, k, t.contiguous().to(dev))
         self._dense_names = tuple(more)
@@ -73,19 +60,15 @@ class HistoryEngine:
         self.lr, self.momentum, self.alpha = float(lr), float(momentum), float(alpha)
         self.reg_p, self.reg_q = float(regs[0]), float(regs[1])
         self.adam = E.AdamState(lr)
-        self.dense = E.make_learner(learner, lr)               # the dense variables' learner; None: ApplyAdam
-        init = {"adam": 0.0, "gd": None, "adagrad": 1e-8, "rmsprop": 1.0, "momentum": 0.0}[learner]
-        two = learner in ("adam", "rmsprop")
-        mk = lambda t, v: None if v is None else torch.full_like(t, v)
-        self.s0 = {k: mk(getattr(self, k), init) for k in self._names}
-        self.s1 = {k: (mk(getattr(self, k), 0.0) if two else None) for k in self._names}
-        rows = learner != "adam"
-        self.flag_Q = torch.zeros(I, dtype=torch.uint8, device=dev) if rows else None
-        self.flag_bias = torch.zeros(I, dtype=torch.uint8, device=dev) if rows else None
+        self.opt = RowLearner(learner, lr, momentum, self.adam)
+        self.dense = self.opt.dense                           # the dense variables' learner; None: ApplyAdam
+        slots = {k: self.opt.slots(getattr(self, k)) for k in self._names}
+        self.s0, self.s1 = ({k: s[i] for k, s in slots.items()} for i in (0, 1))
+        self.flag_Q, self.flag_bias = self.opt.flag(I, dev), self.opt.flag(I, dev)
         # 'rows': c1 gets the sparse application too, on the rows the batch's histories hold (what TF does when the
         # gradient of c1 reaches its optimizer as IndexedSlices); 'dense' (default): the Apply* kernels on every row
         self.c1_rows = c1_application == "rows"
-        self.flag_c1 = torch.zeros(I, dtype=torch.uint8, device=dev) if (rows and self.c1_rows) else None
+        self.flag_c1 = self.opt.flag(I, dev) if self.c1_rows else None
         self.max_batch = int(max_batch)
         N = self._N = max(self.max_batch, 1) * (2 if self.pairwise else 1)         # instances of the largest batch
         self._keys = torch.empty(2 * N, dtype=torch.int64, device=dev)
@@ -97,24 +80,10 @@ class HistoryEngine:
         self.t = 0
 
     def _apply_rows(self, key, flag):
-        var, grad, s0, s1 = getattr(self, key), self.G[key], self.s0[key], self.s1[key]
-        var2, grad2 = var.view(self.n_items, -1), grad.view(self.n_items, -1)
-        v2 = lambda s: None if s is None else s.view(self.n_items, -1)
-        if self.learner == "adam":
-            E.adam_sparse(var, s0, s1, grad, self.adam)
-        elif self.learner == "rmsprop":
-            E.optimizer_rows("rmsprop", var2, v2(s0), v2(s1), grad2, flag, self.lr, 0.9, 0.0, 1e-10)
-        elif self.learner == "momentum":
-            E.optimizer_rows("momentum", var2, v2(s0), None, grad2, flag, self.lr, self.momentum)
-        else:
-            E.optimizer_rows(self.learner, var2, v2(s0), None, grad2, flag, self.lr)
+        self.opt.apply(getattr(self, key), self.s0[key], self.s1[key], self.G[key], flag)
 
     def _apply_dense(self, keys):
-        if self.dense is None:
-            for k in keys:
-                E.adam_dense(getattr(self, k), self.s0[k], self.s1[k], self.G[k], self.adam, clear_grad=False)
-        elif keys:
-            self.dense.apply([(getattr(self, k), self.s0[k], self.s1[k], self.G[k], False) for k in keys])
+        self.opt.apply_dense([(getattr(self, k), self.s0[k], self.s1[k], self.G[k]) for k in keys], clear_grad=False)
 
     def _fill(self, a):
         """the fields of the argument struct beyond the shared ones"""
@@ -140,7 +109,7 @@ class HistoryEngine:
         for k in self._names:
             setattr(a, k, _ptr(getattr(self, k)))
             setattr(a, "G_" + k, _ptr(self.G[k]))
-        a.flag_Q, a.flag_bias, a.flag_c1 = _addr(self.flag_Q), _addr(self.flag_bias), _addr(self.flag_c1)
+        a.flag_Q, a.flag_bias, a.flag_c1 = addr(self.flag_Q), addr(self.flag_bias), addr(self.flag_c1)
         a.users, a.items = self._field(users, torch.int32), self._field(items, torch.int32)
         a.third = self._field(third, torch.int32 if self.pairwise else torch.float32)
         a.keys, a.inst, a.n, a.p, a.scal = (_ptr(t) for t in (self._keys, self._inst, self._n, self._p, self._scal))

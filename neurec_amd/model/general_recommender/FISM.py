@@ -16,7 +16,7 @@ reference raises KeyError).  Candidate mode returns the candidates' entries of t
 from ...util import timer
 from ...util.tool import get_initializer
 from ..AbstractRecommender import AbstractRecommender
-from ._common import predict_scores, train_history_model
+from .._common import predict_scores, require_single_gpu, train_history_model
 
 
 class FISM(AbstractRecommender):
@@ -47,11 +47,8 @@ class FISM(AbstractRecommender):
         self.engine = None
 
     def build_graph(self):
-        from ... import parallel
         from ...fism import FISMEngine
-        if parallel.get_comm().active:
-            raise NotImplementedError("FISM runs on one GPU: a multi-rank run (WORLD_SIZE > 1) is not supported; "
-                                      "start it as a single process")
+        require_single_gpu("FISM")
         init = get_initializer(self.init_method, self.stddev, seed=2017)   # main.py:12
         c1 = init([self.num_items, self.embedding_size])
         Q = init([self.num_items, self.embedding_size])

@@ -15,6 +15,7 @@ leaves "waiting to complete", returns the candidates' entries of the same score 
 import numpy as np
 
 from ...util import timer
+from .._common import require_single_gpu
 from ..AbstractRecommender import AbstractRecommender
 
 
@@ -36,11 +37,8 @@ class ItemKNN(AbstractRecommender):
         self.engine = None
 
     def build_graph(self):
-        from ... import parallel
         from ...itemknn import ItemKNNEngine
-        if parallel.get_comm().active:
-            raise NotImplementedError("ItemKNN runs on one GPU: a multi-rank run (WORLD_SIZE > 1) is not supported; "
-                                      "start it as a single process")
+        require_single_gpu("ItemKNN")
         self.engine = ItemKNNEngine(self.train_matrix, self.topK, self.shrink, self.similarity,
                                     self.asymmetric_alpha, self.tversky_alpha, self.tversky_beta)
 

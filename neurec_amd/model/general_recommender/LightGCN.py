@@ -14,7 +14,7 @@ from ...data import PairwiseSampler
 from ...graph import is_symmetric, lightgcn_adjacency, transpose_csr
 from ...util import timer
 from ..AbstractRecommender import AbstractRecommender
-from ._common import predict_scores
+from .._common import predict_scores
 
 
 class LightGCN(AbstractRecommender):

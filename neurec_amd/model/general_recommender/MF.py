@@ -14,7 +14,7 @@ from ...data import PairwiseSampler, PointwiseSampler
 from ...util import timer
 from ...util.tool import get_initializer
 from ..AbstractRecommender import AbstractRecommender
-from ._common import predict_scores
+from .._common import predict_scores
 
 
 class MF(AbstractRecommender):

@@ -23,7 +23,7 @@ import numpy as np
 from ...util import timer
 from ...util.tool import get_initializer
 from ..AbstractRecommender import AbstractRecommender
-from ._common import train_history_model
+from .._common import require_single_gpu, train_history_model
 
 
 class NAIS(AbstractRecommender):
@@ -64,11 +64,8 @@ class NAIS(AbstractRecommender):
         self.engine = None
 
     def build_graph(self):
-        from ... import parallel
         from ...nais import ACTIVATIONS, MAX_D, MAX_W, NAISEngine, activation_code
-        if parallel.get_comm().active:
-            raise NotImplementedError("NAIS runs on one GPU: a multi-rank run (WORLD_SIZE > 1) is not supported; "
-                                      "start it as a single process")
+        require_single_gpu("NAIS")
         d, w = self.embedding_size, self.weight_size
         if d < 1 or d > MAX_D:
             raise NotImplementedError("NAIS: embedding_size=%d is not supported (1 to %d)" % (d, MAX_D))

@@ -19,7 +19,7 @@ from ...graph import ngcf_adjacency, transpose_csr
 from ...util import timer
 from ...util.tool import get_initializer
 from ..AbstractRecommender import AbstractRecommender
-from ._common import predict_scores
+from .._common import predict_scores
 
 
 class NGCF(AbstractRecommender):

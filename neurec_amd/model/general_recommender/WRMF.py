@@ -14,7 +14,7 @@ from time import time
 from ...util import timer
 from ...util.tool import get_initializer
 from ..AbstractRecommender import AbstractRecommender
-from ._common import predict_scores
+from .._common import predict_scores, require_single_gpu
 
 
 class WRMF(AbstractRecommender):
@@ -35,11 +35,8 @@ class WRMF(AbstractRecommender):
         self.engine = None
 
     def build_graph(self):
-        from ... import parallel
         from ...wrmf import WRMFEngine
-        if parallel.get_comm().active:
-            raise NotImplementedError("WRMF runs on one GPU: a multi-rank run (WORLD_SIZE > 1) is not supported; "
-                                      "start it as a single process")
+        require_single_gpu("WRMF")
         init = get_initializer(self.init_method, self.stddev, seed=2017)   # main.py:12
         users = init([self.num_users, self.embedding_size])
         items = init([self.num_items, self.embedding_size])

@@ -10,14 +10,10 @@ high_order = 1.
 Deviation, on purpose: a user without train items scores <UI_u, IU_i> alone (the reference raises KeyError).
 Candidate mode returns the candidates' entries of the full-mode rows.
 """
-from time import time
-
-import numpy as np
-
 from ...util import timer
 from ...util.tool import get_initializer
 from ..AbstractRecommender import SeqAbstractRecommender
-from ..general_recommender._common import predict_scores
+from .._common import last_item_of, predict_scores, require_single_gpu, train_time_order_model
 
 NO_HISTORY = "users without train items score <UI_u, IU_i> alone (the reference raises KeyError)"
 
@@ -49,11 +45,8 @@ class FPMC(SeqAbstractRecommender):
 
     def build_graph(self):
         import torch
-        from ... import parallel
         from ...fpmc import FPMCEngine
-        if parallel.get_comm().active:
-            raise NotImplementedError("FPMC runs on one GPU: a multi-rank run (WORLD_SIZE > 1) is not supported; "
-                                      "start it as a single process")
+        require_single_gpu("FPMC")
         init = get_initializer(self.init_method, self.stddev, seed=2017)   # main.py:12
         UI = init([self.num_users, self.embedding_size])                   # creation order of FPMC.py:52-59
         IU = init([self.num_items, self.embedding_size])
@@ -61,41 +54,12 @@ class FPMC(SeqAbstractRecommender):
         LI = init([self.num_items, self.embedding_size])
         self.engine = FPMCEngine(UI, IU, IL, LI, self.learning_rate, self.reg_mf, self.batch_size,
                                  loss=self.loss_function, pairwise=self.is_pairwise is True, learner=self.learner)
-        last = np.full(self.num_users, -1, dtype=np.int32)                 # FPMC.py:145-146: cand_items[-1]
-        for user, items in self.train_dict.items():
-            if len(items):
-                last[user] = items[-1]
+        last = last_item_of(self.train_dict, self.num_users)               # FPMC.py:145-146: cand_items[-1]
         self.last_items = torch.from_numpy(last).to(self.engine.UI.device)
 
     # ---------- training process -------
     def train_model(self):
-        import torch
-        from ...data import TimeOrderPairwiseSampler, TimeOrderPointwiseSampler
-        engine = self.engine
-        self.logger.info(self.evaluator.metrics_info())
-        self.logger.info(NO_HISTORY)
-        if self.is_pairwise is True:
-            data_iter = TimeOrderPairwiseSampler(self.dataset, high_order=1, neg_num=1, batch_size=self.batch_size,
-                                                 shuffle=True, as_tensors=True)
-        else:
-            data_iter = TimeOrderPointwiseSampler(self.dataset, high_order=1, neg_num=self.num_negatives,
-                                                  batch_size=self.batch_size, shuffle=True, as_tensors=True)
-        losses = torch.zeros((max(len(data_iter), 1), 2), device=engine.UI.device)
-        for epoch in range(1, self.num_epochs + 1):
-            num_training_instances = len(data_iter)       # FPMC.py:107: the number of BATCHES, kept as it is
-            training_start_time = time()
-            n = 0
-            for bat_users, bat_items_recent, bat_items, bat_third in data_iter:
-                engine.step(bat_users, bat_items_recent, bat_items, bat_third, losses[n])
-                n += 1
-            per_step = losses[:n].cpu().numpy()           # one D2H copy per epoch
-            total_loss = 0.0
-            for a, b in per_step:                          # `total_loss += loss`, FPMC.py:119,128
-                total_loss += np.float32(a) + np.float32(b)
-            self.logger.info("[iter %d : loss : %f, time: %f]" %
-                             (epoch, total_loss / max(num_training_instances, 1), time() - training_start_time))
-            if epoch % self.verbose == 0:
-                self.logger.info("epoch %d:\t%s" % (epoch, self.evaluate()))
+        train_time_order_model(self, 1, self.is_pairwise is True, NO_HISTORY)
 
     @timer
     def evaluate(self):

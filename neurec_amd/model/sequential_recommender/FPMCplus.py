@@ -20,12 +20,11 @@ Deviations, on purpose:
     cannot take.  Here L = 1 trains and scores: alpha = 1, the model is FPMC, and W, b, h move by the regulariser alone.
 Candidate mode returns the candidates' entries of the full-mode rows.
 """
-from time import time
-
 import numpy as np
 
 from ...util import timer
 from ...util.tool import get_initializer
+from .._common import last_items_table, require_single_gpu, train_time_order_model
 from ..AbstractRecommender import SeqAbstractRecommender
 
 DEVIATIONS = "users without train items score <UI_u, IU_i> (the reference raises KeyError); users with fewer than " \
@@ -62,11 +61,8 @@ class FPMCplus(SeqAbstractRecommender):
         self.engine = None
 
     def build_graph(self):
-        from ... import parallel
-        from ...fpmcplus import FPMCplusEngine, last_items_table
-        if parallel.get_comm().active:
-            raise NotImplementedError("FPMCplus runs on one GPU: a multi-rank run (WORLD_SIZE > 1) is not supported; "
-                                      "start it as a single process")
+        from ...fpmcplus import FPMCplusEngine
+        require_single_gpu("FPMCplus")
         d, w = self.embedding_size, self.weight_size
         embed_init = get_initializer(self.embed_init_method, self.stddev, seed=2017)   # main.py:12
         UI = embed_init([self.num_users, d])                   # creation order of FPMCplus.py:58-71
@@ -84,33 +80,9 @@ class FPMCplus(SeqAbstractRecommender):
 
     # ---------- training process -------
     def train_model(self):
-        import torch
-        from ...data import TimeOrderPairwiseSampler, TimeOrderPointwiseSampler
         engine, L = self.engine, self.high_order
-        self.logger.info(self.evaluator.metrics_info())
-        self.logger.info(DEVIATIONS)
-        if self.is_pairwise is True:
-            data_iter = TimeOrderPairwiseSampler(self.dataset, high_order=L, batch_size=self.batch_size, shuffle=True,
-                                                 as_tensors=True)
-        else:
-            data_iter = TimeOrderPointwiseSampler(self.dataset, high_order=L, neg_num=self.num_negatives,
-                                                  batch_size=self.batch_size, shuffle=True, as_tensors=True)
-        losses = torch.zeros((max(len(data_iter), 1), 2), device=engine.UI.device)
-        for epoch in range(1, self.num_epochs + 1):
-            num_training_instances = len(data_iter)       # FPMCplus.py:142: the number of BATCHES, kept as it is
-            training_start_time = time()
-            n = 0
-            for bat_users, bat_items_recent, bat_items, bat_third in data_iter:
-                engine.step(bat_users, bat_items_recent.reshape(-1, L), bat_items, bat_third, losses[n])
-                n += 1
-            per_step = losses[:n].cpu().numpy()           # one D2H copy per epoch
-            total_loss = 0.0
-            for a, b in per_step:                          # `total_loss += loss`, FPMCplus.py:155,165
-                total_loss += np.float32(a) + np.float32(b)
-            self.logger.info("[iter %d : loss : %f, time: %f]" %
-                             (epoch, total_loss / max(num_training_instances, 1), time() - training_start_time))
-            if epoch % self.verbose == 0:
-                self.logger.info("epoch %d:\t%s" % (epoch, self.evaluate()))
+        train_time_order_model(self, L, self.is_pairwise is True, DEVIATIONS,
+                               step=lambda u, recent, i, t, out: engine.step(u, recent.reshape(-1, L), i, t, out))
 
     @timer
     def evaluate(self):

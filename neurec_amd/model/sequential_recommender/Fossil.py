@@ -26,7 +26,7 @@ import numpy as np
 from ...util import timer
 from ...util.tool import get_initializer
 from ..AbstractRecommender import SeqAbstractRecommender
-from ..general_recommender._common import predict_scores
+from .._common import last_items_table, predict_scores, require_single_gpu
 
 STRUCTURE = "instance structure: positive / label 1 = history without the item (n = |R_u| - 1), negative / label 0 = " \
             "whole history (n = |R_u|), users with |R_u| <= high_order skipped; recents most recent first in " \
@@ -43,16 +43,6 @@ def recents_for_engine(recent, high_order):
     if isinstance(recent, np.ndarray):
         return np.ascontiguousarray(recent[:, ::-1])
     return recent.flip(1).contiguous()
-
-
-def last_items_table(train_dict, num_users, high_order):
-    """int32 [U, L]: the items predict() pairs with eta columns 0..L-1 — the last min(L, |R_u|) items of the user's
-    sequence ascending in time from column 0, -1 (the zero row) in the remaining columns"""
-    last = np.full((num_users, high_order), -1, dtype=np.int32)
-    for user, items in train_dict.items():
-        tail = list(items)[max(len(items) - high_order, 0):]
-        last[user, :len(tail)] = tail
-    return last
 
 
 class Fossil(SeqAbstractRecommender):
@@ -86,11 +76,8 @@ class Fossil(SeqAbstractRecommender):
         self.last_items = None
 
     def build_graph(self):
-        from ... import parallel
         from ...fossil import FossilEngine
-        if parallel.get_comm().active:
-            raise NotImplementedError("Fossil runs on one GPU: a multi-rank run (WORLD_SIZE > 1) is not supported; "
-                                      "start it as a single process")
+        require_single_gpu("Fossil")
         init = get_initializer(self.init_method, self.stddev, seed=2017)   # main.py:12
         c1 = init([self.num_items, self.embedding_size])                   # creation order of Fossil.py:63-70
         Q = init([self.num_items, self.embedding_size])

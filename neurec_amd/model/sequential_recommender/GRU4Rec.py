@@ -25,6 +25,7 @@ Candidate mode returns the candidates' entries of the full-mode rows.
 import numpy as np
 
 from ...util.tool import get_initializer
+from .._common import require_single_gpu
 from ..AbstractRecommender import SeqAbstractRecommender
 
 DEVIATIONS = "users without train items score final_act(b), the zero state's row (the reference mis-indexes " \
@@ -116,11 +117,8 @@ class GRU4Rec(SeqAbstractRecommender):
         return data_uit, offset_idx
 
     def build_graph(self):
-        from ... import parallel
         from ...gru4rec import GRU4RecEngine
-        if parallel.get_comm().active:
-            raise NotImplementedError("GRU4Rec runs on one GPU: a multi-rank run (WORLD_SIZE > 1) is not supported; "
-                                      "start it as a single process")
+        require_single_gpu("GRU4Rec")
         n_present = len(self.offset_idx) - 1
         if self.batch_size > n_present:
             raise ValueError("GRU4Rec: batch_size=%d is larger than the %d users with a train item: the "

@@ -29,6 +29,7 @@ Deviations, on purpose — GRU4Rec's three and one more:
 import numpy as np
 
 from ...util.tool import get_initializer
+from .._common import require_single_gpu
 from ..AbstractRecommender import SeqAbstractRecommender
 from .GRU4Rec import DEVIATIONS, GRU4Rec, session_parallel_schedule
 
@@ -84,11 +85,8 @@ class GRU4RecPlus(GRU4Rec):
         self.engine = None
 
     def build_graph(self):
-        from ... import parallel
         from ...gru4recplus import GRU4RecPlusEngine
-        if parallel.get_comm().active:
-            raise NotImplementedError("GRU4RecPlus runs on one GPU: a multi-rank run (WORLD_SIZE > 1) is not supported; "
-                                      "start it as a single process")
+        require_single_gpu("GRU4RecPlus")
         n_present = len(self.offset_idx) - 1
         if self.batch_size > n_present:
             raise ValueError("GRU4RecPlus: batch_size=%d is larger than the %d users with a train item: the "

@@ -15,14 +15,12 @@ Kept: predict() slices `seq[len(seq) - L:]`, so a user with 0 < |R_u| < L is poo
 items (the mean over that many); pre_agg / session_agg values other than "max" mean avg.  Candidate mode returns the
 candidates' entries of the full-mode rows.
 """
-from time import time
-
 import numpy as np
 
 from ...util import timer
 from ...util.tool import get_initializer
 from ..AbstractRecommender import SeqAbstractRecommender
-from ..general_recommender._common import predict_scores
+from .._common import predict_scores, require_single_gpu, train_time_order_model
 
 DEVIATIONS = "users without train items score <P_u, V_i> (the reference raises KeyError); at high_order = 1 " \
              "predict() pools the user with its last item as training does (the reference's concat fails on rank); " \
@@ -67,11 +65,8 @@ class HRM(SeqAbstractRecommender):
         self.last_items = None
 
     def build_graph(self):
-        from ... import parallel
         from ...hrm import HRMEngine
-        if parallel.get_comm().active:
-            raise NotImplementedError("HRM runs on one GPU: a multi-rank run (WORLD_SIZE > 1) is not supported; "
-                                      "start it as a single process")
+        require_single_gpu("HRM")
         init = get_initializer(self.init_method, self.stddev, seed=2017)   # main.py:12
         P = init([self.num_users, self.embedding_size])                    # creation order of HRM.py:49-52
         V = init([self.num_items, self.embedding_size])
@@ -83,29 +78,9 @@ class HRM(SeqAbstractRecommender):
 
     # ---------- training process -------
     def train_model(self):
-        import torch
-        from ...data import TimeOrderPointwiseSampler
         engine, L = self.engine, self.high_order
-        self.logger.info(self.evaluator.metrics_info())
-        self.logger.info(DEVIATIONS)
-        data_iter = TimeOrderPointwiseSampler(self.dataset, high_order=L, neg_num=self.num_negatives,
-                                              batch_size=self.batch_size, shuffle=True, as_tensors=True)
-        losses = torch.zeros((max(len(data_iter), 1), 2), device=engine.P.device)
-        for epoch in range(1, self.num_epochs + 1):
-            num_training_instances = len(data_iter)       # HRM.py:111: the number of BATCHES, kept as it is
-            training_start_time = time()
-            n = 0
-            for bat_users, bat_items_recent, bat_items, bat_labels in data_iter:
-                engine.step(bat_users, bat_items_recent.reshape(-1, L), bat_items, bat_labels, losses[n])
-                n += 1
-            per_step = losses[:n].cpu().numpy()           # one D2H copy per epoch
-            total_loss = 0.0
-            for a, b in per_step:                          # `total_loss += loss`, HRM.py:123
-                total_loss += np.float32(a) + np.float32(b)
-            self.logger.info("[iter %d : loss : %f, time: %f]" %
-                             (epoch, total_loss / max(num_training_instances, 1), time() - training_start_time))
-            if epoch % self.verbose == 0:
-                self.logger.info("epoch %d:\t%s" % (epoch, self.evaluate()))
+        train_time_order_model(self, L, False, DEVIATIONS,
+                               step=lambda u, recent, i, y, out: engine.step(u, recent.reshape(-1, L), i, y, out))
 
     @timer
     def evaluate(self):

@@ -24,6 +24,7 @@ import numpy as np
 
 from ...util import DataIterator, batch_randint_choice, pad_sequences
 from ...util.tool import csr_to_user_dict_bytime, get_initializer
+from .._common import require_single_gpu
 from ..AbstractRecommender import SeqAbstractRecommender
 
 DEVIATIONS = "steps whose batch has no target are skipped and counted (the reference divides 0 by 0); users with one " \
@@ -91,11 +92,8 @@ class SASRec(SeqAbstractRecommender):
         self.engine = None
 
     def build_graph(self):
-        from ... import parallel
         from ...sasrec import SASRecEngine
-        if parallel.get_comm().active:
-            raise NotImplementedError("SASRec runs on one GPU: a multi-rank run (WORLD_SIZE > 1) is not supported; "
-                                      "start it as a single process")
+        require_single_gpu("SASRec")
         d, L = self.hidden_units, self.max_len
         embed = get_initializer("xavier_uniform", 0.01, seed=2017)      # get_variable's default: glorot uniform
         kernel = get_initializer("xavier_uniform", 0.01, seed=2018)     # layers.dense / conv1d: glorot uniform

@@ -17,6 +17,7 @@ import numpy as np
 
 from ...util import timer
 from ...util.tool import get_initializer
+from .._common import last_item_of, require_single_gpu, train_time_order_model
 from ..AbstractRecommender import SeqAbstractRecommender
 
 NO_HISTORY = "users without train items score b_j - |P_u + T - Q_j|, the query without a recent item (the reference " \
@@ -49,11 +50,8 @@ class TransRec(SeqAbstractRecommender):
 
     def build_graph(self):
         import torch
-        from ... import parallel
         from ...transrec import TransRecEngine
-        if parallel.get_comm().active:
-            raise NotImplementedError("TransRec runs on one GPU: a multi-rank run (WORLD_SIZE > 1) is not supported; "
-                                      "start it as a single process")
+        require_single_gpu("TransRec")
         init = get_initializer(self.init_method, self.stddev, seed=2017)   # main.py:12
         P = init([self.num_users, self.embedding_size])                    # creation order of TransRec.py:56-64
         Q = init([self.num_items, self.embedding_size])
@@ -61,41 +59,13 @@ class TransRec(SeqAbstractRecommender):
         T = init([1, self.embedding_size])
         self.engine = TransRecEngine(P, Q, b, T, self.learning_rate, self.reg_mf, self.batch_size,
                                      loss=self.loss_function, pairwise=self.is_pairwise is True, learner=self.learner)
-        last = np.full(self.num_users, -1, dtype=np.int32)                 # TransRec.py:157: train_dict[u][-1]
-        for user, items in self.train_dict.items():
-            if len(items):
-                last[user] = items[-1]
+        last = last_item_of(self.train_dict, self.num_users)               # TransRec.py:157: train_dict[u][-1]
         self.last_items = torch.from_numpy(last).to(self.engine.P.device)
 
     # ---------- training process -------
     def train_model(self):
-        import torch
-        from ...data import TimeOrderPairwiseSampler, TimeOrderPointwiseSampler
-        engine = self.engine
-        self.logger.info(self.evaluator.metrics_info())
-        self.logger.info(NO_HISTORY)
-        if self.is_pairwise is True:
-            data_iter = TimeOrderPairwiseSampler(self.dataset, high_order=1, neg_num=1, batch_size=self.batch_size,
-                                                 shuffle=True, as_tensors=True)
-        else:
-            data_iter = TimeOrderPointwiseSampler(self.dataset, high_order=1, neg_num=self.num_negatives,
-                                                  batch_size=self.batch_size, shuffle=True, as_tensors=True)
-        losses = torch.zeros((max(len(data_iter), 1), 2), device=engine.P.device)
-        self.epoch_losses = []
-        for epoch in range(1, self.num_epochs + 1):
-            num_training_instances = len(data_iter)       # TransRec.py:120: the number of BATCHES, kept as it is
-            n = 0
-            for bat_users, bat_items_recent, bat_items, bat_third in data_iter:
-                engine.step(bat_users, bat_items_recent, bat_items, bat_third, losses[n])
-                n += 1
-            per_step = losses[:n].cpu().numpy()           # one D2H copy per epoch
-            total_loss = 0.0
-            for a, b in per_step:                          # `total_loss += loss`, TransRec.py:132,141
-                total_loss += np.float32(a) + np.float32(b)
-            # TransRec.py:143-144: the reference's `[iter ...]` line is commented out; the figure is kept, not logged
-            self.epoch_losses.append(total_loss / max(num_training_instances, 1))
-            if epoch % self.verbose == 0:
-                self.logger.info("epoch %d:\t%s" % (epoch, self.evaluate()))
+        # TransRec.py:143-144: the reference's `[iter ...]` line is commented out; the figure is kept, not logged
+        train_time_order_model(self, 1, self.is_pairwise is True, NO_HISTORY, log_loss=False)
 
     @timer
     def evaluate(self):

@@ -22,7 +22,8 @@ import torch
 
 from ._lib import NaisScoresArgs, NaisStepArgs, call
 from .engine import _ptr, _stream
-from .history import HistoryEngine, _addr, _f32
+from .history import HistoryEngine
+from .row_learner import addr, f32
 
 MAX_D = 128                   # NRHIP_NAIS_MAX_D
 MAX_W = 64                    # NRHIP_NAIS_MAX_W
@@ -64,13 +65,13 @@ class NAISEngine(HistoryEngine):
             raise ValueError("pair_kernel is 'auto', 'valu' or 'mfma', got %r" % (pair_kernel,))
 
         def attention(d):
-            Wt, bt = _f32(W), _f32(b).reshape(-1)
+            Wt, bt = f32(W), f32(b).reshape(-1)
             if Wt.dim() != 2 or Wt.shape[0] != (algorithm + 1) * d:
                 raise ValueError("W must be [%d, weight_size]" % ((algorithm + 1) * d,))
             w = int(Wt.shape[1])
             if w < 1 or w > MAX_W:
                 raise NotImplementedError("NAIS: weight_size=%d is not supported (1 to %d)" % (w, MAX_W))
-            ht = torch.ones(w) if h is None else _f32(h).reshape(-1)
+            ht = torch.ones(w) if h is None else f32(h).reshape(-1)
             if bt.numel() != w or ht.numel() != w:
                 raise ValueError("b and h must hold weight_size entries")
             return {"W": Wt, "b": bt, "h": ht}
@@ -152,7 +153,7 @@ class NAISEngine(HistoryEngine):
     # ------------------------------------------------------------------ training
     def _fill(self, a):
         a.off, a.rows, a.need = _ptr(self._off), _ptr(self._rows), _ptr(self._need, torch.int64)
-        a.pkeys, a.c1_sort = _addr(self._pkeys), int(self.c1_sort)
+        a.pkeys, a.c1_sort = addr(self._pkeys), int(self.c1_sort)
         a.dWp, a.dbp, a.dhp, a.dqp = _ptr(self._dWp), _ptr(self._dbp), _ptr(self._dhp), _ptr(self._dqp)
         a.row_cap, a.w, a.beta = self.row_cap, self.w, self.beta
         a.algorithm, a.activation, a.reference_mask = self.algorithm, self.activation, int(self.reference_mask)

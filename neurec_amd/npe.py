@@ -3,9 +3,7 @@
 
 An instance is (user, recents r_0..r_{L-1}, item, label): s = the sum of the W rows of the recents,
 q = relu(P[u]) + relu(s), x = <relu(V[i]), q>.  The three tables are read through embedding_lookup only, so TF-1.12
-gives all three the sparse application: Adam's sparse form (every row swept), the row kernels for gd / adagrad /
-rmsprop / momentum — what HRMEngine does for its two tables.  `_apply_rows` and the state allocation repeat HRMEngine's
-on three tables; they are left apart so that fpmc.py and hrm.py stay as they are.
+gives all three the sparse application (neurec_amd/row_learner.py).
 
 The score is a factor form of width d, x(u, i) = <h_u, relu(V[i])> with h_u = relu(P[u]) + relu(sum of W over the
 user's last items) (`last_items`, int32 [U, L], -1 = a slot that takes no part): evaluation is the factor path, its
@@ -13,24 +11,16 @@ item side the transformed table relu(V), which the library writes into a buffer 
 """
 import ctypes as C
 
-import numpy as np
 import torch
 
 from . import engine as E
 from ._lib import NpeStepArgs, call
 from .engine import _ptr, _stream
+from .row_learner import RowLearner, ScoreCache, addr, as_ids, check_loss_learner, f32
 
 MAX_D = 128                   # NRHIP_NPE_MAX_D
 MAX_ORDER = 16                # NRHIP_NPE_MAX_ORDER
 _TABLES = ("P", "V", "W")
-
-
-def _addr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _f32(x):
-    return torch.as_tensor(np.asarray(x), dtype=torch.float32)
 
 
 class NPEEngine:
@@ -42,12 +32,8 @@ class NPEEngine:
 
     def __init__(self, P, V, W, lr, reg, max_batch, high_order, loss="cross_entropy", learner="adam", momentum=0.9,
                  last_items=None):
-        loss, learner = str(loss).lower(), str(learner).lower()
-        if loss not in E.POINTWISE_LOSSES:
-            raise Exception("please choose a suitable loss function")        # learner.py:40
-        if learner != "adam" and learner not in E.ROW_OPTIMIZERS:
-            raise ValueError("please select a suitable optimizer")           # learner.py:15
-        P, V, W = _f32(P), _f32(V), _f32(W)
+        loss, learner, self.loss_kind = check_loss_learner(loss, learner, pairwise=False)
+        P, V, W = f32(P), f32(V), f32(W)
         if P.dim() != 2 or V.dim() != 2 or V.shape[1] != P.shape[1] or W.shape != V.shape:
             raise ValueError("P must be [num_users, embedding_size], V and W [num_items, embedding_size]")
         (U, d), I, L = P.shape, V.shape[0], int(high_order)
@@ -57,20 +43,15 @@ class NPEEngine:
             raise NotImplementedError("NPE: high_order=%d is not supported (1 to %d)" % (L, MAX_ORDER))
         dev = E.require_gpu()
         self.loss, self.learner = loss, learner
-        self.loss_kind = E.POINTWISE_LOSSES[loss]
         self.n_users, self.n_items, self.d, self.L = U, I, d, L
         self.P, self.V, self.W = (t.contiguous().to(dev) for t in (P, V, W))
         self.G = {k: torch.zeros_like(getattr(self, k)) for k in _TABLES}
         self.lr, self.momentum, self.reg = float(lr), float(momentum), float(reg)
         self.adam = E.AdamState(lr)
-        init = {"adam": 0.0, "gd": None, "adagrad": 1e-8, "rmsprop": 1.0, "momentum": 0.0}[learner]
-        two = learner in ("adam", "rmsprop")
-        mk = lambda t, v: None if v is None else torch.full_like(t, v)
-        self.s0 = {k: mk(getattr(self, k), init) for k in _TABLES}
-        self.s1 = {k: (mk(getattr(self, k), 0.0) if two else None) for k in _TABLES}
-        rows = learner != "adam"
-        self.flag = {k: (torch.zeros(getattr(self, k).shape[0], dtype=torch.uint8, device=dev) if rows else None)
-                     for k in _TABLES}
+        self.opt = RowLearner(learner, lr, momentum, self.adam)
+        slots = {k: self.opt.slots(getattr(self, k)) for k in _TABLES}
+        self.s0, self.s1 = ({k: s[i] for k, s in slots.items()} for i in (0, 1))
+        self.flag = {k: self.opt.flag(getattr(self, k).shape[0], dev) for k in _TABLES}
         self.max_batch = int(max_batch)
         N = max(self.max_batch, 1)
         self._keys = torch.empty((2 + L) * N, dtype=torch.int64, device=dev)
@@ -81,18 +62,7 @@ class NPEEngine:
         self.last_items = None if last_items is None else self._last(last_items)
         self._factors = None                                   # (step, h_u of every user)
         self._q = None                                         # (step, relu(V))
-        self._gemm = None
-
-    def _apply_rows(self, key):
-        var, grad, s0, s1, flag = getattr(self, key), self.G[key], self.s0[key], self.s1[key], self.flag[key]
-        if self.learner == "adam":
-            E.adam_sparse(var, s0, s1, grad, self.adam)
-        elif self.learner == "rmsprop":
-            E.optimizer_rows("rmsprop", var, s0, s1, grad, flag, self.lr, 0.9, 0.0, 1e-10)
-        elif self.learner == "momentum":
-            E.optimizer_rows("momentum", var, s0, None, grad, flag, self.lr, self.momentum)
-        else:
-            E.optimizer_rows(self.learner, var, s0, None, grad, flag, self.lr)
+        self._scores = ScoreCache()
 
     def gradients(self, users, recents, items, labels, loss_out):
         """the C call alone: loss_out and the batch's rows of self.G (and the row flags); no table moves"""
@@ -110,7 +80,7 @@ class NPEEngine:
         for k in _TABLES:
             setattr(a, k, _ptr(getattr(self, k)))
             setattr(a, "G_" + k, _ptr(self.G[k]))
-            setattr(a, "flag_" + k, _addr(self.flag[k]))
+            setattr(a, "flag_" + k, addr(self.flag[k]))
         a.users, a.recents, a.items = _ptr(users, torch.int32), _ptr(recents, torch.int32), _ptr(items, torch.int32)
         a.labels = _ptr(labels, torch.float32)
         a.keys, a.scal, a.loss2 = _ptr(self._keys), _ptr(self._scal), _ptr(loss_out, torch.float32)
@@ -122,7 +92,7 @@ class NPEEngine:
     def apply(self):
         """the three applications of self.G; the gradient rows (and flags) are zero again afterwards"""
         for k in _TABLES:
-            self._apply_rows(k)
+            self.opt.apply(getattr(self, k), self.s0[k], self.s1[k], self.G[k], self.flag[k])
         self.adam.advance()
         self.t += 1
 
@@ -134,14 +104,8 @@ class NPEEngine:
 
     # ------------------------------------------------------------------ scoring
     def _last(self, last_items):
-        dev = self.P.device
-        if not isinstance(last_items, torch.Tensor):
-            last_items = torch.from_numpy(np.ascontiguousarray(last_items, dtype=np.int32))
-        last_items = last_items.to(dev, torch.int32).contiguous()
-        if last_items.numel() != self.n_users * self.L:
-            raise ValueError("last_items holds %d entries, not [num_users, high_order] = [%d, %d]" %
-                             (last_items.numel(), self.n_users, self.L))
-        return last_items
+        return as_ids(last_items, self.P.device, self.n_users * self.L,
+                      "last_items holds {n} entries, not [num_users, high_order] = [%d, %d]" % (self.n_users, self.L))
 
     def _need_last(self, last_items):
         if last_items is None:
@@ -184,15 +148,5 @@ class NPEEngine:
 
     def score(self, users, last_items=None):
         """S [n, I] float32 on the device: NPE.py:114-142 for `users`, every item, own items included"""
-        dev = self.P.device
-        if not isinstance(users, torch.Tensor):
-            users = torch.from_numpy(np.ascontiguousarray(users, dtype=np.int32))
-        users = users.to(dev, torch.int32).contiguous()
-        n = int(users.numel())
-        H = self.user_factors(users, last_items)
-        Q = self._item_side()
-        if self._gemm is None or self._gemm.max_rows < n:
-            self._gemm = E.score_gemm_for(Q, max(n, 1))
-        else:
-            self._gemm.prepare(Q)
-        return self._gemm(H, None)[:, :self.n_items]
+        H = self.user_factors(as_ids(users, self.P.device), last_items)
+        return self._scores.score(H, self._item_side(), self.n_items)

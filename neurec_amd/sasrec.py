@@ -24,6 +24,7 @@ import torch
 from . import engine as E
 from ._lib import SasrecStepArgs, SasrecWeights, call
 from .engine import _ptr, _stream
+from .row_learner import as_ids, f32
 
 MAX_BLOCKS = 4                # NRHIP_SASREC_MAX_BLOCKS
 MAX_WIDTH = 128               # NRHIP_SASREC_MAX_WIDTH
@@ -33,10 +34,6 @@ MAX_WEIGHTS = 1 << 30         # NRHIP_SASREC_MAX_WEIGHTS: num_heads * batch * ma
 BETA2 = 0.98                  # SASRec.py:383
 BLOCK_VARS = ("ln1_beta", "ln1_gamma", "Wq", "bq", "Wk", "bk", "Wv", "bv", "ln2_beta", "ln2_gamma", "W1", "b1", "W2",
               "b2")
-
-
-def _f32(x):
-    return torch.as_tensor(np.asarray(x), dtype=torch.float32)
 
 
 def n_sites(num_blocks):
@@ -52,7 +49,7 @@ class SASRecEngine:
     device."""
 
     def __init__(self, item_emb, pos_emb, blocks, final_ln, lr, l2_emb, max_batch, num_heads, dropout_rate, seed=2017):
-        item_emb, pos_emb = _f32(item_emb), _f32(pos_emb)
+        item_emb, pos_emb = f32(item_emb), f32(pos_emb)
         if item_emb.dim() != 2 or pos_emb.dim() != 2 or pos_emb.shape[1] != item_emb.shape[1]:
             raise ValueError("item_emb must be [num_items, hidden_units], pos_emb [max_len, hidden_units]")
         d, L, nb, h = int(item_emb.shape[1]), int(pos_emb.shape[0]), len(blocks), int(num_heads)
@@ -76,7 +73,7 @@ class SASRecEngine:
             raise ValueError("SASRec: dropout_rate=%r outside [0, 1)" % (dropout_rate,))
         fixed = []
         for i, blk in enumerate(blocks):
-            blk = [_f32(t) for t in blk]
+            blk = [f32(t) for t in blk]
             if len(blk) != len(BLOCK_VARS):
                 raise ValueError("block %d: %d arrays, want %s" % (i, len(blk), ", ".join(BLOCK_VARS)))
             out = []
@@ -86,7 +83,7 @@ class SASRecEngine:
                     raise ValueError("block %d: %s holds %d values, want %d" % (i, name, t.numel(), want))
                 out.append(t.reshape(d, d) if name.startswith("W") else t.reshape(d))
             fixed.append(out)
-        final_ln = [_f32(t).reshape(-1) for t in final_ln]
+        final_ln = [f32(t).reshape(-1) for t in final_ln]
         if len(final_ln) != 2 or any(t.numel() != d for t in final_ln):
             raise ValueError("final_ln must be (beta [hidden_units], gamma [hidden_units])")
         dev = E.require_gpu()
@@ -138,9 +135,7 @@ class SASRecEngine:
             raise ValueError("SASRec: %s holds an item outside [0, %d]" % (name, self.n_items))
 
     def _ids(self, a):
-        if not isinstance(a, torch.Tensor):
-            a = torch.from_numpy(np.ascontiguousarray(a))
-        return a.to(self.item_emb.device, torch.int32).contiguous()
+        return as_ids(a, self.item_emb.device)
 
     # ------------------------------------------------------------------ training
     def gradients(self, seq, pos, neg, loss_out, masks=None):

@@ -6,33 +6,25 @@ distance x = b_i - |v|^2; predict() ranks by b_j - |P_u + T + Q_last(u) - Q_j|, 
 is read as the recent item, as the target and as the negative in the same batch.
 
 Optimiser forms, as TF-1.12 picks them: P, Q and b are read through embedding_lookup only — the sparse application
-(Adam's sparse form, every row swept; the row kernels for gd / adagrad / rmsprop / momentum), b as HistoryEngine's
-`bias`; T is read through tf.tile — the dense Apply* kernels, every step.
+(neurec_amd/row_learner.py), b as a [num_items, 1] table; T is read through tf.tile — the dense Apply* kernels, every
+step.
 
 The score has no factor form: evaluation has a kernel of its own, the direct-difference distance.
 """
 import ctypes as C
 
-import numpy as np
 import torch
 
 from . import engine as E
 from ._lib import TransrecStepArgs, call
 from .engine import _ptr, _stream
+from .row_learner import RowLearner, addr, as_ids, check_loss_learner, f32
 
 MAX_D = 128                   # NRHIP_TRANSREC_MAX_D
 GT_CHUNK = 32                 # NRHIP_TRANSREC_CHUNK: instances per partial sum of G_T
 GT_MAX_CHUNKS = 64            # NRHIP_TRANSREC_MAX_CHUNKS
 _ROWS = ("P", "Q", "b")
 _TABLES = _ROWS + ("T",)
-
-
-def _addr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _f32(x):
-    return torch.as_tensor(np.asarray(x), dtype=torch.float32)
 
 
 class TransRecEngine:
@@ -43,13 +35,8 @@ class TransRecEngine:
     the device."""
 
     def __init__(self, P, Q, b, T, lr, reg_mf, max_batch, loss="bpr", pairwise=True, learner="adam", momentum=0.9):
-        loss, learner = str(loss).lower(), str(learner).lower()
-        table = E.PAIRWISE_LOSSES if pairwise else E.POINTWISE_LOSSES
-        if loss not in table:
-            raise Exception("please choose a suitable loss function")        # learner.py:28,40
-        if learner != "adam" and learner not in E.ROW_OPTIMIZERS:
-            raise ValueError("please select a suitable optimizer")           # learner.py:15
-        P, Q, b, T = _f32(P), _f32(Q), _f32(b).reshape(-1), _f32(T).reshape(-1)
+        loss, learner, self.loss_kind = check_loss_learner(loss, learner, pairwise)
+        P, Q, b, T = f32(P), f32(Q), f32(b).reshape(-1), f32(T).reshape(-1)
         if P.dim() != 2 or Q.dim() != 2 or Q.shape[1] != P.shape[1]:
             raise ValueError("P must be [num_users, embedding_size], Q [num_items, embedding_size]")
         (U, d), I = P.shape, Q.shape[0]
@@ -59,23 +46,16 @@ class TransRecEngine:
             raise ValueError("b must hold num_items entries and T embedding_size entries")
         dev = E.require_gpu()
         self.loss, self.pairwise, self.learner = loss, bool(pairwise), learner
-        self.loss_kind = table[loss]
         self.n_users, self.n_items, self.d = U, I, d
         self.P, self.Q, self.b, self.T = (t.contiguous().to(dev) for t in (P, Q, b, T))
         self.G = {k: torch.zeros_like(getattr(self, k)) for k in _TABLES}
         self.lr, self.momentum, self.reg_mf = float(lr), float(momentum), float(reg_mf)
         self.adam = E.AdamState(lr)
-        self.dense = E.make_learner(learner, lr)               # T; None: ApplyAdam
-        if self.dense is not None:
-            self.dense.momentum = self.momentum
-        init = {"adam": 0.0, "gd": None, "adagrad": 1e-8, "rmsprop": 1.0, "momentum": 0.0}[learner]
-        two = learner in ("adam", "rmsprop")
-        mk = lambda t, v: None if v is None else torch.full_like(t, v)
-        self.s0 = {k: mk(getattr(self, k), init) for k in _TABLES}
-        self.s1 = {k: (mk(getattr(self, k), 0.0) if two else None) for k in _TABLES}
-        rows = learner != "adam"
-        self.flag = {k: (torch.zeros(getattr(self, k).shape[0], dtype=torch.uint8, device=dev) if rows else None)
-                     for k in _ROWS}
+        self.opt = RowLearner(learner, lr, momentum, self.adam)
+        self.dense = self.opt.dense                           # T; None: ApplyAdam
+        slots = {k: self.opt.slots(getattr(self, k)) for k in _TABLES}
+        self.s0, self.s1 = ({k: s[i] for k, s in slots.items()} for i in (0, 1))
+        self.flag = {k: self.opt.flag(getattr(self, k).shape[0], dev) for k in _ROWS}
         self.max_batch = int(max_batch)
         mb = max(self.max_batch, 1)
         self._keys = torch.empty(3 * mb * (2 if self.pairwise else 1), dtype=torch.int64, device=dev)
@@ -85,25 +65,6 @@ class TransRecEngine:
         self.t = 0
 
     # ------------------------------------------------------------------ training
-    def _apply_rows(self, key):
-        var, grad, s0, s1, flag = getattr(self, key), self.G[key], self.s0[key], self.s1[key], self.flag[key]
-        rows = var.shape[0]
-        v2 = lambda s: None if s is None else s.view(rows, -1)
-        if self.learner == "adam":
-            E.adam_sparse(var, s0, s1, grad, self.adam)
-        elif self.learner == "rmsprop":
-            E.optimizer_rows("rmsprop", v2(var), v2(s0), v2(s1), v2(grad), flag, self.lr, 0.9, 0.0, 1e-10)
-        elif self.learner == "momentum":
-            E.optimizer_rows("momentum", v2(var), v2(s0), None, v2(grad), flag, self.lr, self.momentum)
-        else:
-            E.optimizer_rows(self.learner, v2(var), v2(s0), None, v2(grad), flag, self.lr)
-
-    def _apply_dense(self):
-        if self.dense is None:
-            E.adam_dense(self.T, self.s0["T"], self.s1["T"], self.G["T"], self.adam, clear_grad=True)
-        else:
-            self.dense.apply([(self.T, self.s0["T"], self.s1["T"], self.G["T"], True)])
-
     def gradients(self, users, recent, items, third, loss_out):
         """the C call alone: loss_out, the batch's rows of G_P / G_Q / G_b (and the row flags) and G_T whole; no table
         moves.  An empty batch is no work: nothing is launched and loss_out is set to zero."""
@@ -120,7 +81,7 @@ class TransRecEngine:
             setattr(a, k, _ptr(getattr(self, k)))
             setattr(a, "G_" + k, _ptr(self.G[k]))
         for k in _ROWS:
-            setattr(a, "flag_" + k, _addr(self.flag[k]))
+            setattr(a, "flag_" + k, addr(self.flag[k]))
         a.users, a.recent, a.items = _ptr(users, torch.int32), _ptr(recent, torch.int32), _ptr(items, torch.int32)
         a.third = _ptr(third, torch.int32 if self.pairwise else torch.float32)
         a.keys, a.scal, a.partial = _ptr(self._keys), _ptr(self._scal), _ptr(self._partial)
@@ -133,8 +94,8 @@ class TransRecEngine:
         """three sparse applications and the dense one of T; the gradient buffers (and flags) are zero again
         afterwards"""
         for k in _ROWS:
-            self._apply_rows(k)
-        self._apply_dense()
+            self.opt.apply(getattr(self, k), self.s0[k], self.s1[k], self.G[k], self.flag[k])
+        self.opt.apply_dense([(self.T, self.s0["T"], self.s1["T"], self.G["T"])], clear_grad=True)
         self.adam.advance()
         self.t += 1
 
@@ -147,28 +108,15 @@ class TransRecEngine:
             self.apply()
 
     # ------------------------------------------------------------------ scoring
-    def _last(self, last_items):
-        if not isinstance(last_items, torch.Tensor):
-            last_items = torch.from_numpy(np.ascontiguousarray(last_items, dtype=np.int32))
-        last_items = last_items.to(self.P.device, torch.int32).contiguous()
-        if last_items.numel() != self.n_users:
-            raise ValueError("last_items holds %d entries, the user table %d rows" % (last_items.numel(), self.n_users))
-        return last_items
-
-    def _users(self, users):
-        if users is None:
-            return None
-        if not isinstance(users, torch.Tensor):
-            users = torch.from_numpy(np.ascontiguousarray(users, dtype=np.int32))
-        return users.to(self.P.device, torch.int32).contiguous()
-
     def queries(self, last_items, users=None):
         """[n, d] rows P_u + T + Q_last(u) of `users` (None: every user); last -1: P_u + T"""
-        users = self._users(users)
+        dev = self.P.device
+        users = None if users is None else as_ids(users, dev)
+        last = as_ids(last_items, dev, self.n_users, "last_items holds {n} entries, the user table {want} rows")
         n = self.n_users if users is None else int(users.numel())
-        out = torch.empty((n, self.d), dtype=torch.float32, device=self.P.device)
+        out = torch.empty((n, self.d), dtype=torch.float32, device=dev)
         call("nrhip_transrec_queries", _ptr(self.P), _ptr(self.Q), _ptr(self.T), self.n_users, self.n_items, self.d,
-             _ptr(self._last(last_items), torch.int32), _ptr(users, torch.int32, allow_none=True), n, _ptr(out),
+             _ptr(last, torch.int32), _ptr(users, torch.int32, allow_none=True), n, _ptr(out),
              out.stride(0), _stream())
         return out
 
