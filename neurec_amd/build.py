@@ -29,8 +29,8 @@ FILE_FLAGS = {"score_i8.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 # nothing of it is linked into the product
 EXP_SOURCES = ["experiments/gather_experiments.hip"]
 EXP_LIB_PATH = os.path.join(HERE, "libneurec_exp.so")
-HEADERS = ["nr_core.h", "nr_common.h", "history_common.h", "spmm_blocked_plan.h", "spmm_blocked_factor.h",
-           "spmm_wanted_plan.h", "gru4rec_cell.h"]
+HEADERS = ["nr_core.h", "nr_common.h", "rowkey_common.h", "history_common.h", "spmm_blocked_plan.h",
+           "spmm_blocked_factor.h", "spmm_wanted_plan.h", "gru4rec_cell.h"]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-ffp-contract=off",

@@ -162,14 +162,6 @@ __global__ __launch_bounds__(256) void fism_factors_kernel(const int64_t* __rest
 
 }  // namespace
 
-#define NR_FISM_BY_WIDTH(KERNEL, grid, st, ...)                                                  \
-  do {                                                                                           \
-    if (d <= 16) hipLaunchKernelGGL((KERNEL<16, 1>), grid, dim3(256), 0, st, __VA_ARGS__);       \
-    else if (d <= 32) hipLaunchKernelGGL((KERNEL<32, 1>), grid, dim3(256), 0, st, __VA_ARGS__);  \
-    else if (d <= 64) hipLaunchKernelGGL((KERNEL<64, 1>), grid, dim3(256), 0, st, __VA_ARGS__);  \
-    else hipLaunchKernelGGL((KERNEL<64, 2>), grid, dim3(256), 0, st, __VA_ARGS__);               \
-  } while (0)
-
 extern "C" {
 
 int nrhip_fism_step(const nrhip_fism_step_args* args, void* stream) {
@@ -194,7 +186,7 @@ int nrhip_fism_step(const nrhip_fism_step_args* args, void* stream) {
     hipLaunchKernelGGL(prepare_kernel<nrhip_fism_step_args>, dim3((N + 255) / 256), dim3(256), 0, st, a, N);
     NR_LAUNCH_CHECK();
     NR_TRY(nrhip_sort_u64(a.d_keys, 2 * N, stream));
-    NR_FISM_BY_WIDTH(fism_forward_kernel, dim3((N + 3) / 4), st, a, N);
+    NR_BY_WIDTH(fism_forward_kernel, d, dim3((N + 3) / 4), st, a, N);
     NR_LAUNCH_CHECK();
   }
   hipLaunchKernelGGL(loss_kernel<nrhip_fism_step_args>, dim3(1), dim3(256), 0, st, a, N);
@@ -220,7 +212,7 @@ int nrhip_fism_user_factors(const int64_t* d_indptr, const int32_t* d_indices, i
                  (d_users || batch <= n_users), NR_ERR_ARG, "fism_user_factors: bad arguments");
   if (batch == 0) return NR_OK;
   hipStream_t st = (hipStream_t)stream;
-  NR_FISM_BY_WIDTH(fism_factors_kernel, dim3((batch + 3) / 4), st, d_indptr, d_indices, n_users, d_c1, d, alpha,
+  NR_BY_WIDTH(fism_factors_kernel, d, dim3((batch + 3) / 4), st, d_indptr, d_indices, n_users, d_c1, d, alpha,
                    d_users, batch, d_out, ld);
   NR_LAUNCH_CHECK();
   return NR_OK;

@@ -327,14 +327,6 @@ __global__ __launch_bounds__(256) void fossil_factors_kernel(const int64_t* __re
 
 }  // namespace
 
-#define NR_FOSSIL_BY_WIDTH(KERNEL, grid, st, ...)                                                \
-  do {                                                                                           \
-    if (d <= 16) hipLaunchKernelGGL((KERNEL<16, 1>), grid, dim3(256), 0, st, __VA_ARGS__);       \
-    else if (d <= 32) hipLaunchKernelGGL((KERNEL<32, 1>), grid, dim3(256), 0, st, __VA_ARGS__);  \
-    else if (d <= 64) hipLaunchKernelGGL((KERNEL<64, 1>), grid, dim3(256), 0, st, __VA_ARGS__);  \
-    else hipLaunchKernelGGL((KERNEL<64, 2>), grid, dim3(256), 0, st, __VA_ARGS__);               \
-  } while (0)
-
 extern "C" {
 
 int nrhip_fossil_step(const nrhip_fossil_step_args* args, void* stream) {
@@ -363,7 +355,7 @@ int nrhip_fossil_step(const nrhip_fossil_step_args* args, void* stream) {
                        N);
     NR_LAUNCH_CHECK();
     NR_TRY(nrhip_sort_u64(a.d_keys, 2 * N, stream));
-    NR_FOSSIL_BY_WIDTH(fossil_forward_kernel, dim3((N + 3) / 4), st, a, N);
+    NR_BY_WIDTH(fossil_forward_kernel, d, dim3((N + 3) / 4), st, a, N);
     NR_LAUNCH_CHECK();
   }
   hipLaunchKernelGGL((loss_kernel<nrhip_fossil_step_args, FossilRule>), dim3(1), dim3(256), 0, st, a, N);
@@ -396,7 +388,7 @@ int nrhip_fossil_user_factors(const int64_t* d_indptr, const int32_t* d_indices,
              "fossil_user_factors: bad arguments");
   if (batch == 0) return NR_OK;
   hipStream_t st = (hipStream_t)stream;
-  NR_FOSSIL_BY_WIDTH(fossil_factors_kernel, dim3((batch + 3) / 4), st, d_indptr, d_indices, n_users, n_items, d_c1,
+  NR_BY_WIDTH(fossil_factors_kernel, d, dim3((batch + 3) / 4), st, d_indptr, d_indices, n_users, n_items, d_c1,
                      d_eta, d_eta_bias, d_last, d, L, alpha, d_users, batch, d_out, ld);
   NR_LAUNCH_CHECK();
   return NR_OK;

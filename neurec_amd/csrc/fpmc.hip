@@ -14,7 +14,7 @@
 //                             keys [N, 2N)    IU / IL row n_users + i | j   (one run serves both tables: same index)
 //                             keys [2N, 3N)   LI row n_users + n_items + l  at positions t and B + t
 //                         a slot that takes no part writes the sentinel key and g = 0
-//   fpmc_loss_kernel      one workgroup: the loss and regulariser sums in a fixed order
+//   loss_kernel           rowkey_common.h: one workgroup, the loss and regulariser sums in a fixed order
 //   nrhip_sort_u64        the keys, ascending
 //   fpmc_rows_kernel      one lane group per sorted key: the head of a run walks it and STORES the row's gradient,
 //                         every occurrence recomputed from the gathered rows: g * partner row + reg * own row
@@ -22,22 +22,16 @@
 //   fpmc_factors_kernel   [UI[u] | LI[last(u)]] per user: the evaluation's user factors against [IU | IL]
 //
 // Every float sum is taken in a fixed order and nothing is accumulated with atomics: two runs are bit-identical.
-#include "nr_common.h"
+#include "rowkey_common.h"
 #include "neurec_hip.h"
 
 namespace {
 
-constexpr uint64_t kSentinel = 0x7fffffffffffffffull;     // a slot that takes no part sorts behind every key
-constexpr int kScal = 4;                                  // floats per batch slot in d_scal
-enum { S_G = 0, S_LOSS = 1, S_L2 = 2 };
-
-__device__ __forceinline__ uint64_t row_key(int row, int pos) { return ((uint64_t)(uint32_t)row << 32) | (uint32_t)pos; }
+using namespace nr::rowkey;
 
 template <int DP, int CPL>
 __global__ __launch_bounds__(256) void fpmc_forward_kernel(nrhip_fpmc_step_args a) {
-  constexpr int G = NR_WAVE / DP;
-  const int lane = threadIdx.x & 63, c = lane % DP;
-  const int t = (blockIdx.x * 4 + (threadIdx.x >> 6)) * G + lane / DP;
+  const int c = group_lane<DP>(), t = group_index<DP>();
   const int B = a.batch, d = a.d, U = a.n_users, I = a.n_items;
   const int N = a.pairwise ? 2 * B : B;
   const bool in = t < B;
@@ -68,7 +62,8 @@ __global__ __launch_bounds__(256) void fpmc_forward_kernel(nrhip_fpmc_step_args 
       }
     }
   }
-  // groups are DP-aligned: the xor partners of a lane are lanes of its own group
+  // group_sum's tree in the kernel's own text: through the helper the compiler issues the loads of d_third and of the
+  // flag pointers behind the tree instead of ahead of it, and the step measured 0.2 us slower
 #pragma unroll
   for (int m = DP / 2; m >= 1; m >>= 1) {
     xi += __shfl_xor(xi, m, NR_WAVE);
@@ -78,17 +73,7 @@ __global__ __launch_bounds__(256) void fpmc_forward_kernel(nrhip_fpmc_step_args 
   if (!in || c != 0) return;
   float g = 0.f, loss = 0.f;
   if (ok) {
-    if (a.pairwise) {
-      const float y = xi - xj;
-      loss = nr::pairwise_loss(a.loss_kind, y);
-      g = nr::pairwise_dloss(a.loss_kind, y);
-    } else {
-      // tf.losses.sigmoid_cross_entropy is a MEAN over the batch, every other loss of util/learner.py a sum
-      const float scale = a.loss_kind == nr::NR_POINT_CROSS_ENTROPY ? 1.0f / (float)B : 1.0f;
-      const float z = ((const float*)a.d_third)[t];
-      loss = scale * nr::pointwise_loss(a.loss_kind, z, xi);
-      g = scale * nr::pointwise_dloss(a.loss_kind, z, xi);
-    }
+    instance_loss_g(a.pairwise, a.loss_kind, B, a.d_third, t, xi, xj, loss, g);
     if (a.d_flag_UI) a.d_flag_UI[u] = 1;
     if (a.d_flag_LI) a.d_flag_LI[l] = 1;
     if (a.d_flag_IU) a.d_flag_IU[i] = 1;
@@ -98,10 +83,7 @@ __global__ __launch_bounds__(256) void fpmc_forward_kernel(nrhip_fpmc_step_args 
       if (a.d_flag_IL) a.d_flag_IL[j] = 1;
     }
   }
-  float* sc = a.d_scal + (int64_t)t * kScal;
-  sc[S_G] = g;
-  sc[S_LOSS] = loss;
-  sc[S_L2] = ok ? 0.5f * sq : 0.f;
+  store_slot(a.d_scal + (int64_t)t * kScal, g, loss, sq, ok);
   a.d_keys[t] = ok ? row_key(u, t) : kSentinel;
   a.d_keys[N + t] = ok ? row_key(U + i, t) : kSentinel;
   a.d_keys[2 * (int64_t)N + t] = ok ? row_key(U + I + l, t) : kSentinel;
@@ -112,60 +94,29 @@ __global__ __launch_bounds__(256) void fpmc_forward_kernel(nrhip_fpmc_step_args 
   }
 }
 
-__global__ __launch_bounds__(256) void fpmc_loss_kernel(nrhip_fpmc_step_args a) {
-  __shared__ double s_a[256], s_b[256];
-  double la = 0.0, lb = 0.0;
-  for (int t = threadIdx.x; t < a.batch; t += 256) {
-    const float* sc = a.d_scal + (int64_t)t * kScal;
-    la += (double)sc[S_LOSS];
-    lb += (double)sc[S_L2];
-  }
-  s_a[threadIdx.x] = la;
-  s_b[threadIdx.x] = lb;
-  __syncthreads();
-  for (int s = 128; s >= 1; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-      s_a[threadIdx.x] += s_a[threadIdx.x + s];
-      s_b[threadIdx.x] += s_b[threadIdx.x + s];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    a.d_loss2[0] = (float)s_a[0];
-    a.d_loss2[1] = (float)((double)a.reg * s_b[0]);
-  }
-}
-
 // the sum of one run of the sorted keys: own row `own` of the table, per occurrence g * partner row (+ reg * own row)
 template <int DP, int CPL>
 __global__ __launch_bounds__(256) void fpmc_rows_kernel(nrhip_fpmc_step_args a) {
-  constexpr int G = NR_WAVE / DP;
-  const int lane = threadIdx.x & 63, c = lane % DP;
-  const int64_t w = (int64_t)(blockIdx.x * 4 + (threadIdx.x >> 6)) * G + lane / DP;
+  const int c = group_lane<DP>();
+  const int64_t w = group_index<DP, int64_t>();
   const int B = a.batch, d = a.d, U = a.n_users, I = a.n_items;
   const int64_t n_keys = 3 * (int64_t)(a.pairwise ? 2 * B : B);
-  if (w >= n_keys) return;
-  const uint64_t key = a.d_keys[w];
-  if (key == kSentinel) return;
-  const uint32_t row = (uint32_t)(key >> 32);
-  if (w > 0 && (uint32_t)(a.d_keys[w - 1] >> 32) == row) return;            // not the head of its run
+  const int row = head_row(a.d_keys, n_keys, w);
+  if (row < 0) return;
   const float reg = a.reg;
   const int32_t* negs = (const int32_t*)a.d_third;
-  if ((int)row >= U && (int)row < U + I) {
+  if (row >= U && row < U + I) {
     // an item as the target of an inference: its IU row against UI[u], its IL row against LI[l]
-    const int item = (int)row - U;
-    float own_u[CPL], own_l[CPL], acc_u[CPL], acc_l[CPL];
+    const int item = row - U;
+    float own_u[CPL], own_l[CPL], acc_u[CPL] = {}, acc_l[CPL] = {};
 #pragma unroll
-    for (int k = 0; k < CPL; ++k) {
+    for (int k = 0; k < CPL; ++k) {                        // both rows in one pass: two load_row calls wait in turn
       const int col = c + k * DP;
-      acc_u[k] = acc_l[k] = 0.f;
       own_u[k] = col < d ? a.d_IU[(int64_t)item * d + col] : 0.f;
       own_l[k] = col < d ? a.d_IL[(int64_t)item * d + col] : 0.f;
     }
-    for (int64_t q = w; q < n_keys; ++q) {
-      const uint64_t kk = a.d_keys[q];
-      if ((uint32_t)(kk >> 32) != row) break;
-      const int pos = (int)(uint32_t)kk;
+    for_run(a.d_keys, n_keys, w, row, [&](uint32_t low) {
+      const int pos = (int)low;
       const int t = pos >= B ? pos - B : pos;
       const float g0 = a.d_scal[(int64_t)t * kScal + S_G], g = pos >= B ? -g0 : g0;
       const int u = a.d_users[t], l = a.d_recent[t];
@@ -177,35 +128,22 @@ __global__ __launch_bounds__(256) void fpmc_rows_kernel(nrhip_fpmc_step_args a) 
           acc_l[k] += g * a.d_LI[(int64_t)l * d + col] + reg * own_l[k];
         }
       }
-    }
-#pragma unroll
-    for (int k = 0; k < CPL; ++k) {
-      const int col = c + k * DP;
-      if (col < d) {
-        a.d_G_IU[(int64_t)item * d + col] = acc_u[k];
-        a.d_G_IL[(int64_t)item * d + col] = acc_l[k];
-      }
-    }
+    });
+    store_row<DP, CPL>(a.d_G_IU, item, d, c, acc_u);
+    store_row<DP, CPL>(a.d_G_IL, item, d, c, acc_l);
     return;
   }
   // a user's UI row against IU[item], or a recent item's LI row against IL[item]; the lookup of the second
   // inference carries the gradient through the negative's score and no regulariser term
-  const bool is_user = (int)row < U;
-  const int r = is_user ? (int)row : (int)row - U - I;
+  const bool is_user = row < U;
+  const int r = is_user ? row : row - U - I;
   const float* table = is_user ? a.d_UI : a.d_LI;
   const float* partner = is_user ? a.d_IU : a.d_IL;
   float* dst = is_user ? a.d_G_UI : a.d_G_LI;
-  float own[CPL], acc[CPL];
-#pragma unroll
-  for (int k = 0; k < CPL; ++k) {
-    const int col = c + k * DP;
-    acc[k] = 0.f;
-    own[k] = col < d ? table[(int64_t)r * d + col] : 0.f;
-  }
-  for (int64_t q = w; q < n_keys; ++q) {
-    const uint64_t kk = a.d_keys[q];
-    if ((uint32_t)(kk >> 32) != row) break;
-    const int pos = (int)(uint32_t)kk;
+  float own[CPL], acc[CPL] = {};
+  load_row<DP, CPL>(table, r, d, c, own);
+  for_run(a.d_keys, n_keys, w, row, [&](uint32_t low) {
+    const int pos = (int)low;
     const bool second = pos >= B;
     const int t = second ? pos - B : pos;
     const float g0 = a.d_scal[(int64_t)t * kScal + S_G];
@@ -218,12 +156,8 @@ __global__ __launch_bounds__(256) void fpmc_rows_kernel(nrhip_fpmc_step_args a) 
         acc[k] += second ? -g0 * p : g0 * p + reg * own[k];
       }
     }
-  }
-#pragma unroll
-  for (int k = 0; k < CPL; ++k) {
-    const int col = c + k * DP;
-    if (col < d) dst[(int64_t)r * d + col] = acc[k];
-  }
+  });
+  store_row<DP, CPL>(dst, r, d, c, acc);
 }
 
 __global__ __launch_bounds__(256) void fpmc_factors_kernel(const float* __restrict__ UI, const float* __restrict__ LI,
@@ -249,15 +183,6 @@ __global__ __launch_bounds__(256) void fpmc_factors_kernel(const float* __restri
 
 }  // namespace
 
-// lane groups sized to d: KERNEL<lanes per row, columns per lane>
-#define NR_FPMC_BY_WIDTH(KERNEL, d, groups, st, ...)                                                          \
-  do {                                                                                                        \
-    if ((d) <= 16) hipLaunchKernelGGL((KERNEL<16, 1>), dim3(((groups) + 15) / 16), dim3(256), 0, st, __VA_ARGS__);      \
-    else if ((d) <= 32) hipLaunchKernelGGL((KERNEL<32, 1>), dim3(((groups) + 7) / 8), dim3(256), 0, st, __VA_ARGS__);   \
-    else if ((d) <= 64) hipLaunchKernelGGL((KERNEL<64, 1>), dim3(((groups) + 3) / 4), dim3(256), 0, st, __VA_ARGS__);   \
-    else hipLaunchKernelGGL((KERNEL<64, 2>), dim3(((groups) + 3) / 4), dim3(256), 0, st, __VA_ARGS__);                  \
-  } while (0)
-
 extern "C" {
 
 int nrhip_fpmc_step(const nrhip_fpmc_step_args* args, void* stream) {
@@ -270,23 +195,18 @@ int nrhip_fpmc_step(const nrhip_fpmc_step_args* args, void* stream) {
              "fpmc_step: null pointer argument");
   NR_REQUIRE(a.batch >= 0 && a.batch <= NRHIP_FPMC_MAX_BATCH && a.n_users >= 0 && a.n_items >= 0 &&
                  (int64_t)a.n_users + 2 * (int64_t)a.n_items < ((int64_t)1 << 31) - 1, NR_ERR_ARG, "fpmc_step: bad sizes");
-  if (a.pairwise)
-    NR_REQUIRE(a.loss_kind >= nr::NR_PAIR_BPR && a.loss_kind <= nr::NR_PAIR_SQUARE, NR_ERR_ARG,
-               "fpmc_step: unknown pairwise loss %d (0 bpr, 1 hinge, 2 square)", a.loss_kind);
-  else
-    NR_REQUIRE(a.loss_kind == nr::NR_POINT_CROSS_ENTROPY || a.loss_kind == nr::NR_POINT_SQUARE, NR_ERR_ARG,
-               "fpmc_step: unknown pointwise loss %d (0 cross_entropy, 1 square)", a.loss_kind);
+  NR_TRY(check_loss_kind("fpmc_step", a.pairwise, a.loss_kind));
   hipStream_t st = (hipStream_t)stream;
   const int B = a.batch, n_keys = 3 * B * (a.pairwise ? 2 : 1);
   if (B > 0) {
-    NR_FPMC_BY_WIDTH(fpmc_forward_kernel, a.d, B, st, a);
+    NR_BY_WIDTH(fpmc_forward_kernel, a.d, B, st, a);
     NR_LAUNCH_CHECK();
     NR_TRY(nrhip_sort_u64(a.d_keys, n_keys, stream));
   }
-  hipLaunchKernelGGL(fpmc_loss_kernel, dim3(1), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(loss_kernel<nrhip_fpmc_step_args>, dim3(1), dim3(256), 0, st, a);
   NR_LAUNCH_CHECK();
   if (B > 0) {
-    NR_FPMC_BY_WIDTH(fpmc_rows_kernel, a.d, n_keys, st, a);
+    NR_BY_WIDTH(fpmc_rows_kernel, a.d, n_keys, st, a);
     NR_LAUNCH_CHECK();
   }
   return NR_OK;

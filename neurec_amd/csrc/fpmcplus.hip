@@ -31,17 +31,14 @@
 //                             wavefront walks the block's users with the pair's L logits and L + 1 products in registers
 //
 // Every float sum is taken in a fixed order and nothing is accumulated with atomics: two runs are bit-identical.
-#include "nr_common.h"
+#include "rowkey_common.h"
 #include "neurec_hip.h"
 
 namespace {
 
-constexpr uint64_t kSentinel = 0x7fffffffffffffffull;     // a slot that takes no part sorts behind every key
-constexpr int kScal = 4;                                  // floats per batch slot in d_scal
-enum { S_G = 0, S_LOSS = 1, S_L2 = 2, S_OK = 3 };
-constexpr int kChunks = NRHIP_FPMCPLUS_MAX_CHUNKS;
+using namespace nr::rowkey;
 
-__device__ __forceinline__ uint64_t row_key(int row, uint32_t idx) { return ((uint64_t)(uint32_t)row << 32) | idx; }
+constexpr int kChunks = NRHIP_FPMCPLUS_MAX_CHUNKS;
 
 __host__ __device__ inline int chunks_of(int B) { return B <= 0 ? 0 : (B + 31) / 32 < kChunks ? (B + 31) / 32 : kChunks; }
 
@@ -276,59 +273,36 @@ __global__ __launch_bounds__(64) void fpmcplus_instance_kernel(nrhip_fpmcplus_st
 }
 
 __global__ __launch_bounds__(256) void fpmcplus_loss_kernel(nrhip_fpmcplus_step_args a) {
-  __shared__ double s_a[256], s_b[256], s_c[256];
-  double la = 0.0, lb = 0.0, lc = 0.0;
-  for (int t = threadIdx.x; t < a.batch; t += 256) {
-    const float* sc = a.d_scal + (int64_t)t * kScal;
-    la += (double)sc[S_LOSS];
-    lb += (double)sc[S_L2];
-  }
+  double v[3] = {0.0, 0.0, 0.0};                           // the loss, the rows' l2 sum, |W|^2 + |h|^2
+  slot_sums(a.d_scal, a.batch, v[0], v[1]);
   if (a.pairwise) {                                        // reg_w l2_loss(W, h): the pairwise loss alone has it
-    for (int e = threadIdx.x; e < 3 * a.d * a.w; e += 256) lc += (double)a.d_W[e] * (double)a.d_W[e];
-    for (int e = threadIdx.x; e < a.w; e += 256) lc += (double)a.d_h[e] * (double)a.d_h[e];
+    for (int e = threadIdx.x; e < 3 * a.d * a.w; e += 256) v[2] += (double)a.d_W[e] * (double)a.d_W[e];
+    for (int e = threadIdx.x; e < a.w; e += 256) v[2] += (double)a.d_h[e] * (double)a.d_h[e];
   }
-  s_a[threadIdx.x] = la;
-  s_b[threadIdx.x] = lb;
-  s_c[threadIdx.x] = lc;
-  __syncthreads();
-  for (int s = 128; s >= 1; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-      s_a[threadIdx.x] += s_a[threadIdx.x + s];
-      s_b[threadIdx.x] += s_b[threadIdx.x + s];
-      s_c[threadIdx.x] += s_c[threadIdx.x + s];
-    }
-    __syncthreads();
-  }
+  block_sum(v);
   if (threadIdx.x == 0) {
-    a.d_loss2[0] = (float)s_a[0];
-    a.d_loss2[1] = (float)((double)a.reg_mf * s_b[0] + (double)a.reg_w * 0.5 * s_c[0]);
+    a.d_loss2[0] = (float)v[0];
+    a.d_loss2[1] = (float)((double)a.reg_mf * v[1] + (double)a.reg_w * 0.5 * v[2]);
   }
 }
 
-// the sum of one run of the sorted keys: the contributions of the row's occurrences, added in key order and stored
-template <int DP>
+// the sum of one run of the sorted keys: the contributions of the row's occurrences, added in key order and stored.
+// The column loop strides by DP: the columns per lane of the launch ladder are not used
+template <int DP, int>
 __global__ __launch_bounds__(256) void fpmcplus_rows_kernel(nrhip_fpmcplus_step_args a, int n_keys) {
-  constexpr int G = NR_WAVE / DP;
-  const int lane = threadIdx.x & 63, c0 = lane % DP;
-  const int64_t q0 = (int64_t)(blockIdx.x * 4 + (threadIdx.x >> 6)) * G + lane / DP;
-  if (q0 >= n_keys) return;
-  const uint64_t key = a.d_keys[q0];
-  if (key == kSentinel) return;
-  const uint32_t row = (uint32_t)(key >> 32);
-  if (q0 > 0 && (uint32_t)(a.d_keys[q0 - 1] >> 32) == row) return;          // not the head of its run
+  const int c0 = group_lane<DP>();
+  const int64_t q0 = group_index<DP, int64_t>();
+  const int head = head_row(a.d_keys, n_keys, q0);
+  if (head < 0) return;
   const int d = a.d, U = a.n_users, I = a.n_items;
   float* dst;
-  if ((int)row < U) dst = a.d_G_UI + (int64_t)row * d;
-  else if ((int)row < U + I) dst = a.d_G_IU + (int64_t)((int)row - U) * d;
-  else if ((int)row < U + 2 * I) dst = a.d_G_IL + (int64_t)((int)row - U - I) * d;
-  else dst = a.d_G_LI + (int64_t)((int)row - U - 2 * I) * d;
+  if (head < U) dst = a.d_G_UI + (int64_t)head * d;
+  else if (head < U + I) dst = a.d_G_IU + (int64_t)(head - U) * d;
+  else if (head < U + 2 * I) dst = a.d_G_IL + (int64_t)(head - U - I) * d;
+  else dst = a.d_G_LI + (int64_t)(head - U - 2 * I) * d;
   for (int c = c0; c < d; c += DP) {
     float acc = 0.f;
-    for (int64_t q = q0; q < n_keys; ++q) {
-      const uint64_t kk = a.d_keys[q];
-      if ((uint32_t)(kk >> 32) != row) break;
-      acc += a.d_contrib[(int64_t)(uint32_t)kk * d + c];
-    }
+    for_run(a.d_keys, n_keys, q0, head, [&](uint32_t idx) { acc += a.d_contrib[(int64_t)idx * d + c]; });
     dst[c] = acc;
   }
 }
@@ -508,12 +482,7 @@ int nrhip_fpmcplus_step(const nrhip_fpmcplus_step_args* args, void* stream) {
   NR_REQUIRE(a.batch >= 0 && a.batch <= NRHIP_FPMCPLUS_MAX_BATCH && a.n_users >= 0 && a.n_items >= 0 &&
                  (int64_t)a.n_users + 3 * (int64_t)a.n_items < ((int64_t)1 << 31) - 1, NR_ERR_ARG,
              "fpmcplus_step: bad sizes");
-  if (a.pairwise)
-    NR_REQUIRE(a.loss_kind >= nr::NR_PAIR_BPR && a.loss_kind <= nr::NR_PAIR_SQUARE, NR_ERR_ARG,
-               "fpmcplus_step: unknown pairwise loss %d (0 bpr, 1 hinge, 2 square)", a.loss_kind);
-  else
-    NR_REQUIRE(a.loss_kind == nr::NR_POINT_CROSS_ENTROPY || a.loss_kind == nr::NR_POINT_SQUARE, NR_ERR_ARG,
-               "fpmcplus_step: unknown pointwise loss %d (0 cross_entropy, 1 square)", a.loss_kind);
+  NR_TRY(check_loss_kind("fpmcplus_step", a.pairwise, a.loss_kind));
   const int B = a.batch;
   if (B == 0) return NR_OK;                                // no work: nothing is launched, nothing is written
   NR_REQUIRE(a.d_UI && a.d_IU && a.d_IL && a.d_LI && a.d_W && a.d_b && a.d_h && a.d_G_UI && a.d_G_IU && a.d_G_IL &&
@@ -531,9 +500,7 @@ int nrhip_fpmcplus_step(const nrhip_fpmcplus_step_args* args, void* stream) {
   NR_TRY(nrhip_sort_u64(a.d_keys, n_keys, stream));
   hipLaunchKernelGGL(fpmcplus_loss_kernel, dim3(1), dim3(256), 0, st, a);
   NR_LAUNCH_CHECK();
-  if (d <= 16) hipLaunchKernelGGL((fpmcplus_rows_kernel<16>), dim3((n_keys + 15) / 16), dim3(256), 0, st, a, n_keys);
-  else if (d <= 32) hipLaunchKernelGGL((fpmcplus_rows_kernel<32>), dim3((n_keys + 7) / 8), dim3(256), 0, st, a, n_keys);
-  else hipLaunchKernelGGL((fpmcplus_rows_kernel<64>), dim3((n_keys + 3) / 4), dim3(256), 0, st, a, n_keys);
+  NR_BY_WIDTH(fpmcplus_rows_kernel, d, n_keys, st, a, n_keys);
   NR_LAUNCH_CHECK();
   hipLaunchKernelGGL(fpmcplus_dense_kernel, dim3((n_el + 255) / 256, chunks), dim3(256), 0, st, a, chunks);
   NR_LAUNCH_CHECK();

@@ -13,14 +13,15 @@
 //
 // The kernels are templates over the argument struct: nrhip_fism_step_args, nrhip_nais_step_args and
 // nrhip_fossil_step_args name every field read here alike.  A model whose instances differ from FISM's names a Rule
-// (PlainRule: FISM's and NAIS's).  Every float sum is taken in a fixed order.
+// (PlainRule: FISM's and NAIS's).  Every float sum is taken in a fixed order.  The sentinel, the head test under
+// run_head, loss_kernel's tree and the width ladder (NR_BY_WIDTH) are rowkey_common.h's.
 #pragma once
-#include "nr_common.h"
+#include "rowkey_common.h"
 
 namespace nr {
 namespace hist {
 
-constexpr uint64_t kSentinel = 0x7fffffffffffffffull;     // an instance that takes no part sorts behind every key
+using rowkey::kSentinel;                                  // an instance that takes no part sorts behind every key
 constexpr int kScal = 8;                                  // floats per instance in d_scal; slots 5..7 are the model's
 // S_RSQ: the square sum reg_p multiplies (FISM: |p|^2; NAIS: the history rows' |c1[h]|^2)
 enum { S_OUT = 0, S_COEFF = 1, S_RSQ = 2, S_QSQ = 3, S_DOUT = 4 };
@@ -113,11 +114,11 @@ __device__ __forceinline__ void pool_row(const int64_t* __restrict__ indptr, con
 
 template <class Args, class Rule = PlainRule>
 __global__ __launch_bounds__(256) void loss_kernel(Args a, int N) {
-  __shared__ double s_a[256], s_b[256];
   const int B = a.batch;
   // tf.losses.sigmoid_cross_entropy is a MEAN over the batch, every other loss of util/learner.py a sum
   const float scale = (!a.pairwise && a.loss_kind == nr::NR_POINT_CROSS_ENTROPY) ? 1.0f / (float)B : 1.0f;
-  double la = 0.0, lb = 0.0;
+  double v[2] = {0.0, 0.0};
+  double &la = v[0], &lb = v[1];
   for (int t = threadIdx.x; t < B; t += 256) {
     float* sp = a.d_scal + (int64_t)t * kScal;
     if (!(a.d_inst[4 * t + 3] & F_VALID)) continue;
@@ -138,19 +139,10 @@ __global__ __launch_bounds__(256) void loss_kernel(Args a, int N) {
       if constexpr (Rule::kExtraReg) lb += Rule::extra_reg(a, sp);
     }
   }
-  s_a[threadIdx.x] = la;
-  s_b[threadIdx.x] = lb;
-  __syncthreads();
-  for (int s = 128; s >= 1; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-      s_a[threadIdx.x] += s_a[threadIdx.x + s];
-      s_b[threadIdx.x] += s_b[threadIdx.x + s];
-    }
-    __syncthreads();
-  }
+  rowkey::block_sum(v);
   if (threadIdx.x == 0 && a.d_loss2) {
-    a.d_loss2[0] = (float)s_a[0];
-    a.d_loss2[1] = (float)s_b[0];
+    a.d_loss2[0] = (float)la;
+    a.d_loss2[1] = (float)lb;
   }
 }
 
@@ -158,12 +150,9 @@ __global__ __launch_bounds__(256) void loss_kernel(Args a, int N) {
 // keys: a user, or n_users + item).  The head of a user's run publishes the user's slot on the way.
 template <class Args>
 __device__ __forceinline__ int run_head(const Args& a, int w, int lane) {
-  const uint64_t key = a.d_keys[w];
-  if (key == kSentinel) return -1;
-  const uint32_t row = (uint32_t)(key >> 32);
-  if (w > 0 && (uint32_t)(a.d_keys[w - 1] >> 32) == row) return -1;         // not the head of its run
-  if ((int)row < a.n_users && lane == 0) a.d_slot[row] = ((int64_t)a.step << 32) | (uint32_t)w;
-  return (int)row;
+  const int row = rowkey::head_row(a.d_keys, w);
+  if (row >= 0 && row < a.n_users && lane == 0) a.d_slot[row] = ((int64_t)a.step << 32) | (uint32_t)w;
+  return row;
 }
 
 // run_head for the heads of the items' runs alone

@@ -24,23 +24,19 @@
 //                             keys [B, 2B)         V row n_users + i at position t
 //                             keys [2B, 2B + B L)  V row n_users + r at position B + t L + l
 //                         a slot that takes no part writes the sentinel key and g = 0
-//   hrm_loss_kernel       one workgroup: the loss and regulariser sums in a fixed order
+//   loss_kernel           rowkey_common.h: one workgroup, the loss and regulariser sums in a fixed order
 //   nrhip_sort_u64        the keys, ascending
 //   hrm_rows_kernel       one lane group per sorted key: the head of a run walks it and STORES the row's gradient
 //   hrm_factors_kernel    h_u per user from a [U][L] table of last items: pool_session and pool_pre again
 //
 // Nothing is kept per (slot, recent): no [B][L][d] block exists.  Every float sum is taken in a fixed order and
 // nothing is accumulated with atomics: two runs are bit-identical.
-#include "nr_common.h"
+#include "rowkey_common.h"
 #include "neurec_hip.h"
 
 namespace {
 
-constexpr uint64_t kSentinel = 0x7fffffffffffffffull;     // a slot that takes no part sorts behind every key
-constexpr int kScal = 4;                                  // floats per batch slot in d_scal
-enum { S_G = 0, S_LOSS = 1, S_L2 = 2 };
-
-__device__ __forceinline__ uint64_t row_key(int row, uint32_t pos) { return ((uint64_t)(uint32_t)row << 32) | pos; }
+using namespace nr::rowkey;
 
 // The session row of `L` item ids (entries outside [0, n_items) are skipped), columns c + k DP of one lane: the
 // column-wise max with cnt = the number of rows that hold it, or the mean (cnt = the number of rows pooled).  One row
@@ -96,9 +92,7 @@ __device__ __forceinline__ float pool_pre(float p, float s, bool use_max, float&
 
 template <int DP, int CPL>
 __global__ __launch_bounds__(256) void hrm_forward_kernel(nrhip_hrm_step_args a) {
-  constexpr int G = NR_WAVE / DP;
-  const int lane = threadIdx.x & 63, c = lane % DP;
-  const int t = (blockIdx.x * 4 + (threadIdx.x >> 6)) * G + lane / DP;
+  const int c = group_lane<DP>(), t = group_index<DP>();
   const int B = a.batch, d = a.d, U = a.n_users, I = a.n_items, L = a.L;
   const bool in = t < B;
   const bool session_max = a.session_max && L > 1, pre_max = a.pre_max != 0;
@@ -109,11 +103,8 @@ __global__ __launch_bounds__(256) void hrm_forward_kernel(nrhip_hrm_step_args a)
     if (c < L) r_mine = a.d_recents[(int64_t)t * L + c];            // L <= 16 <= DP: lane c holds recent c
   }
   // an instance takes part as a whole or not at all: every lookup must be a table row
-  int bad = !in || u < 0 || u >= U || i < 0 || i >= I || (c < L && (r_mine < 0 || r_mine >= I));
-  // groups are DP-aligned: the xor partners of a lane are lanes of its own group
-#pragma unroll
-  for (int m = DP / 2; m >= 1; m >>= 1) bad |= __shfl_xor(bad, m, NR_WAVE);
-  const bool ok = !bad;
+  const int bad = !in || u < 0 || u >= U || i < 0 || i >= I || (c < L && (r_mine < 0 || r_mine >= I));
+  const bool ok = !group_any<DP>(bad);
   float x = 0.f, sq = 0.f;
   float s[CPL], cnt[CPL], vi[CPL], share_s[CPL];
 #pragma unroll
@@ -133,19 +124,11 @@ __global__ __launch_bounds__(256) void hrm_forward_kernel(nrhip_hrm_step_args a)
       }
     }
   }
-#pragma unroll
-  for (int m = DP / 2; m >= 1; m >>= 1) {
-    x += __shfl_xor(x, m, NR_WAVE);
-    sq += __shfl_xor(sq, m, NR_WAVE);
-  }
+  group_sum<DP>(x, sq);
   if (!in) return;
   float g = 0.f, loss = 0.f;
   if (ok) {
-    // tf.losses.sigmoid_cross_entropy is a MEAN over the batch, every other loss of util/learner.py a sum
-    const float scale = a.loss_kind == nr::NR_POINT_CROSS_ENTROPY ? 1.0f / (float)B : 1.0f;
-    const float z = a.d_labels[t];
-    loss = scale * nr::pointwise_loss(a.loss_kind, z, x);
-    g = scale * nr::pointwise_dloss(a.loss_kind, z, x);
+    pointwise_loss_g(a.loss_kind, B, a.d_labels[t], x, loss, g);
 #pragma unroll
     for (int k = 0; k < CPL; ++k) {
       const int col = c + k * DP;
@@ -164,68 +147,29 @@ __global__ __launch_bounds__(256) void hrm_forward_kernel(nrhip_hrm_step_args a)
     if (a.d_flag_P) a.d_flag_P[u] = 1;
     if (a.d_flag_V) a.d_flag_V[i] = 1;
   }
-  float* sc = a.d_scal + (int64_t)t * kScal;
-  sc[S_G] = g;
-  sc[S_LOSS] = loss;
-  sc[S_L2] = ok ? 0.5f * sq : 0.f;
+  store_slot(a.d_scal + (int64_t)t * kScal, g, loss, sq, ok);
   a.d_keys[t] = ok ? row_key(u, (uint32_t)t) : kSentinel;
   a.d_keys[(int64_t)B + t] = ok ? row_key(U + i, (uint32_t)t) : kSentinel;
-}
-
-__global__ __launch_bounds__(256) void hrm_loss_kernel(nrhip_hrm_step_args a) {
-  __shared__ double s_a[256], s_b[256];
-  double la = 0.0, lb = 0.0;
-  for (int t = threadIdx.x; t < a.batch; t += 256) {
-    const float* sc = a.d_scal + (int64_t)t * kScal;
-    la += (double)sc[S_LOSS];
-    lb += (double)sc[S_L2];
-  }
-  s_a[threadIdx.x] = la;
-  s_b[threadIdx.x] = lb;
-  __syncthreads();
-  for (int s = 128; s >= 1; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-      s_a[threadIdx.x] += s_a[threadIdx.x + s];
-      s_b[threadIdx.x] += s_b[threadIdx.x + s];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    a.d_loss2[0] = (float)s_a[0];
-    a.d_loss2[1] = (float)((double)a.reg * s_b[0]);
-  }
 }
 
 // the sum of one run of the sorted keys
 template <int DP, int CPL>
 __global__ __launch_bounds__(256) void hrm_rows_kernel(nrhip_hrm_step_args a) {
-  constexpr int G = NR_WAVE / DP;
-  const int lane = threadIdx.x & 63, c = lane % DP;
-  const int64_t w = (int64_t)(blockIdx.x * 4 + (threadIdx.x >> 6)) * G + lane / DP;
+  const int c = group_lane<DP>();
+  const int64_t w = group_index<DP, int64_t>();
   const int B = a.batch, d = a.d, U = a.n_users, L = a.L;
   const int64_t n_keys = (int64_t)B * (2 + L);
-  if (w >= n_keys) return;
-  const uint64_t key = a.d_keys[w];
-  if (key == kSentinel) return;
-  const uint32_t row = (uint32_t)(key >> 32);
-  if (w > 0 && (uint32_t)(a.d_keys[w - 1] >> 32) == row) return;            // not the head of its run
+  const int row = head_row(a.d_keys, n_keys, w);
+  if (row < 0) return;
   const float reg = a.reg;
   const bool session_max = a.session_max && L > 1, pre_max = a.pre_max != 0;
-  const bool is_user = (int)row < U;
-  const int r = is_user ? (int)row : (int)row - U;
+  const bool is_user = row < U;
+  const int r = is_user ? row : row - U;
   const float* table = is_user ? a.d_P : a.d_V;
   float* dst = is_user ? a.d_G_P : a.d_G_V;
-  float own[CPL], acc[CPL];
-#pragma unroll
-  for (int k = 0; k < CPL; ++k) {
-    const int col = c + k * DP;
-    acc[k] = 0.f;
-    own[k] = col < d ? table[(int64_t)r * d + col] : 0.f;
-  }
-  for (int64_t q = w; q < n_keys; ++q) {
-    const uint64_t kk = a.d_keys[q];
-    if ((uint32_t)(kk >> 32) != row) break;
-    const uint32_t pos = (uint32_t)kk;
+  float own[CPL], acc[CPL] = {};
+  load_row<DP, CPL>(table, r, d, c, own);
+  for_run(a.d_keys, n_keys, w, row, [&](uint32_t pos) {
     if (is_user || pos < (uint32_t)B) {
       // the user's row: its share of g V[i]; the target's row: g h — both from P[u] and the slot's s
       const int t = (int)pos;
@@ -255,12 +199,8 @@ __global__ __launch_bounds__(256) void hrm_rows_kernel(nrhip_hrm_step_args a) {
         }
       }
     }
-  }
-#pragma unroll
-  for (int k = 0; k < CPL; ++k) {
-    const int col = c + k * DP;
-    if (col < d) dst[(int64_t)r * d + col] = acc[k];
-  }
+  });
+  store_row<DP, CPL>(dst, r, d, c, acc);
 }
 
 template <int DP, int CPL>
@@ -269,9 +209,7 @@ __global__ __launch_bounds__(256) void hrm_factors_kernel(const float* __restric
                                                           int session_max, const int32_t* __restrict__ last,
                                                           const int32_t* __restrict__ users, int batch,
                                                           float* __restrict__ out, int64_t ld) {
-  constexpr int G = NR_WAVE / DP;
-  const int lane = threadIdx.x & 63, c = lane % DP;
-  const int b = (blockIdx.x * 4 + (threadIdx.x >> 6)) * G + lane / DP;
+  const int c = group_lane<DP>(), b = group_index<DP>();
   if (b >= batch) return;
   const int u = users ? users[b] : b;
   float s[CPL], cnt[CPL], sq = 0.f;
@@ -295,15 +233,6 @@ __global__ __launch_bounds__(256) void hrm_factors_kernel(const float* __restric
 
 }  // namespace
 
-// lane groups sized to d: KERNEL<lanes per row, columns per lane>
-#define NR_HRM_BY_WIDTH(KERNEL, d, groups, st, ...)                                                                    \
-  do {                                                                                                                 \
-    if ((d) <= 16) hipLaunchKernelGGL((KERNEL<16, 1>), dim3((unsigned)(((groups) + 15) / 16)), dim3(256), 0, st, __VA_ARGS__);    \
-    else if ((d) <= 32) hipLaunchKernelGGL((KERNEL<32, 1>), dim3((unsigned)(((groups) + 7) / 8)), dim3(256), 0, st, __VA_ARGS__); \
-    else if ((d) <= 64) hipLaunchKernelGGL((KERNEL<64, 1>), dim3((unsigned)(((groups) + 3) / 4)), dim3(256), 0, st, __VA_ARGS__); \
-    else hipLaunchKernelGGL((KERNEL<64, 2>), dim3((unsigned)(((groups) + 3) / 4)), dim3(256), 0, st, __VA_ARGS__);                \
-  } while (0)
-
 extern "C" {
 
 int nrhip_hrm_step(const nrhip_hrm_step_args* args, void* stream) {
@@ -317,20 +246,19 @@ int nrhip_hrm_step(const nrhip_hrm_step_args* args, void* stream) {
                  a.d_scal && a.d_s && a.d_ds && a.d_loss2, NR_ERR_ARG, "hrm_step: null pointer argument");
   NR_REQUIRE(a.batch >= 0 && a.batch <= NRHIP_HRM_MAX_BATCH && a.n_users >= 0 && a.n_items >= 0 &&
                  (int64_t)a.n_users + (int64_t)a.n_items < ((int64_t)1 << 31) - 1, NR_ERR_ARG, "hrm_step: bad sizes");
-  NR_REQUIRE(a.loss_kind == nr::NR_POINT_CROSS_ENTROPY || a.loss_kind == nr::NR_POINT_SQUARE, NR_ERR_ARG,
-             "hrm_step: unknown pointwise loss %d (0 cross_entropy, 1 square)", a.loss_kind);
+  NR_TRY(check_loss_kind("hrm_step", 0, a.loss_kind));
   hipStream_t st = (hipStream_t)stream;
   const int B = a.batch;
   const int64_t n_keys = (int64_t)B * (2 + a.L);
   if (B > 0) {
-    NR_HRM_BY_WIDTH(hrm_forward_kernel, a.d, (int64_t)B, st, a);
+    NR_BY_WIDTH(hrm_forward_kernel, a.d, B, st, a);
     NR_LAUNCH_CHECK();
     NR_TRY(nrhip_sort_u64(a.d_keys, (int)n_keys, stream));
   }
-  hipLaunchKernelGGL(hrm_loss_kernel, dim3(1), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(loss_kernel<nrhip_hrm_step_args>, dim3(1), dim3(256), 0, st, a);
   NR_LAUNCH_CHECK();
   if (B > 0) {
-    NR_HRM_BY_WIDTH(hrm_rows_kernel, a.d, n_keys, st, a);
+    NR_BY_WIDTH(hrm_rows_kernel, a.d, n_keys, st, a);
     NR_LAUNCH_CHECK();
   }
   return NR_OK;
@@ -347,7 +275,7 @@ int nrhip_hrm_user_factors(const float* d_P, const float* d_V, int n_users, int 
                  (d_users || batch <= n_users), NR_ERR_ARG, "hrm_user_factors: bad arguments");
   if (batch == 0) return NR_OK;
   hipStream_t st = (hipStream_t)stream;
-  NR_HRM_BY_WIDTH(hrm_factors_kernel, d, (int64_t)batch, st, d_P, d_V, n_users, n_items, d, L, pre_max, session_max,
+  NR_BY_WIDTH(hrm_factors_kernel, d, batch, st, d_P, d_V, n_users, n_items, d, L, pre_max, session_max,
                   d_last, d_users, batch, d_out, ld);
   NR_LAUNCH_CHECK();
   return NR_OK;

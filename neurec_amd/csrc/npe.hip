@@ -27,7 +27,7 @@
 //                             keys [B, 2B)         V row U + i         at position t
 //                             keys [2B, 2B + B L)  W row U + I + r_l   at position t L + l
 //                         a slot that takes no part writes the sentinel key and g = 0
-//   npe_loss_kernel       one workgroup: the loss and regulariser sums in a fixed order, in double
+//   loss_kernel           rowkey_common.h: one workgroup, the loss and regulariser sums in a fixed order, in double
 //   nrhip_sort_u64        the keys, ascending
 //   npe_rows_kernel       one lane group per sorted key: the head of a run walks it and STORES the row's gradient
 //   npe_factors_kernel    h_u = relu(P[u]) + relu(sum of W[last[u][l]]) per user: context_sum and gate_q again
@@ -35,16 +35,12 @@
 //
 // Nothing is kept per (slot, recent): no [B][L][d] block exists.  Every float sum is taken in a fixed order and
 // nothing is accumulated with atomics: two runs are bit-identical.
-#include "nr_common.h"
+#include "rowkey_common.h"
 #include "neurec_hip.h"
 
 namespace {
 
-constexpr uint64_t kSentinel = 0x7fffffffffffffffull;     // a slot that takes no part sorts behind every key
-constexpr int kScal = 4;                                  // floats per batch slot in d_scal
-enum { S_G = 0, S_LOSS = 1, S_L2 = 2 };
-
-__device__ __forceinline__ uint64_t row_key(int row, uint32_t pos) { return ((uint64_t)(uint32_t)row << 32) | pos; }
+using namespace nr::rowkey;
 
 // TF's Relu and the indicator of its ReluGrad: strictly positive inputs pass, 0 and -0 do not
 __device__ __forceinline__ float relu(float x) { return x > 0.f ? x : 0.f; }
@@ -78,9 +74,7 @@ __device__ __forceinline__ float gate_q(float p, float s) { return relu(p) + rel
 
 template <int DP, int CPL>
 __global__ __launch_bounds__(256) void npe_forward_kernel(nrhip_npe_step_args a) {
-  constexpr int G = NR_WAVE / DP;
-  const int lane = threadIdx.x & 63, c = lane % DP;
-  const int t = (blockIdx.x * 4 + (threadIdx.x >> 6)) * G + lane / DP;
+  const int c = group_lane<DP>(), t = group_index<DP>();
   const int B = a.batch, d = a.d, U = a.n_users, I = a.n_items, L = a.L;
   const bool in = t < B;
   int u = -1, i = -1, r_mine = 0;
@@ -90,11 +84,8 @@ __global__ __launch_bounds__(256) void npe_forward_kernel(nrhip_npe_step_args a)
     if (c < L) r_mine = a.d_recents[(int64_t)t * L + c];            // L <= 16 <= DP: lane c holds recent c
   }
   // an instance takes part as a whole or not at all: every lookup must be a table row
-  int bad = !in || u < 0 || u >= U || i < 0 || i >= I || (c < L && (r_mine < 0 || r_mine >= I));
-  // groups are DP-aligned: the xor partners of a lane are lanes of its own group
-#pragma unroll
-  for (int m = DP / 2; m >= 1; m >>= 1) bad |= __shfl_xor(bad, m, NR_WAVE);
-  const bool ok = !bad;
+  const int bad = !in || u < 0 || u >= U || i < 0 || i >= I || (c < L && (r_mine < 0 || r_mine >= I));
+  const bool ok = !group_any<DP>(bad);
   float x = 0.f, sq = 0.f;
   float s[CPL], rv[CPL];
 #pragma unroll
@@ -112,19 +103,11 @@ __global__ __launch_bounds__(256) void npe_forward_kernel(nrhip_npe_step_args a)
       }
     }
   }
-#pragma unroll
-  for (int m = DP / 2; m >= 1; m >>= 1) {
-    x += __shfl_xor(x, m, NR_WAVE);
-    sq += __shfl_xor(sq, m, NR_WAVE);
-  }
+  group_sum<DP>(x, sq);
   if (!in) return;
   float g = 0.f, loss = 0.f;
   if (ok) {
-    // tf.losses.sigmoid_cross_entropy is a MEAN over the batch, every other loss of util/learner.py a sum
-    const float scale = a.loss_kind == nr::NR_POINT_CROSS_ENTROPY ? 1.0f / (float)B : 1.0f;
-    const float z = a.d_labels[t];
-    loss = scale * nr::pointwise_loss(a.loss_kind, z, x);
-    g = scale * nr::pointwise_dloss(a.loss_kind, z, x);
+    pointwise_loss_g(a.loss_kind, B, a.d_labels[t], x, loss, g);
 #pragma unroll
     for (int k = 0; k < CPL; ++k) {
       const int col = c + k * DP;
@@ -143,67 +126,28 @@ __global__ __launch_bounds__(256) void npe_forward_kernel(nrhip_npe_step_args a)
     if (a.d_flag_P) a.d_flag_P[u] = 1;
     if (a.d_flag_V) a.d_flag_V[i] = 1;
   }
-  float* sc = a.d_scal + (int64_t)t * kScal;
-  sc[S_G] = g;
-  sc[S_LOSS] = loss;
-  sc[S_L2] = ok ? 0.5f * sq : 0.f;
+  store_slot(a.d_scal + (int64_t)t * kScal, g, loss, sq, ok);
   a.d_keys[t] = ok ? row_key(u, (uint32_t)t) : kSentinel;
   a.d_keys[(int64_t)B + t] = ok ? row_key(U + i, (uint32_t)t) : kSentinel;
-}
-
-__global__ __launch_bounds__(256) void npe_loss_kernel(nrhip_npe_step_args a) {
-  __shared__ double s_a[256], s_b[256];
-  double la = 0.0, lb = 0.0;
-  for (int t = threadIdx.x; t < a.batch; t += 256) {
-    const float* sc = a.d_scal + (int64_t)t * kScal;
-    la += (double)sc[S_LOSS];
-    lb += (double)sc[S_L2];
-  }
-  s_a[threadIdx.x] = la;
-  s_b[threadIdx.x] = lb;
-  __syncthreads();
-  for (int s = 128; s >= 1; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-      s_a[threadIdx.x] += s_a[threadIdx.x + s];
-      s_b[threadIdx.x] += s_b[threadIdx.x + s];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    a.d_loss2[0] = (float)s_a[0];
-    a.d_loss2[1] = (float)((double)a.reg * s_b[0]);
-  }
 }
 
 // the sum of one run of the sorted keys
 template <int DP, int CPL>
 __global__ __launch_bounds__(256) void npe_rows_kernel(nrhip_npe_step_args a) {
-  constexpr int G = NR_WAVE / DP;
-  const int lane = threadIdx.x & 63, c = lane % DP;
-  const int64_t w = (int64_t)(blockIdx.x * 4 + (threadIdx.x >> 6)) * G + lane / DP;
+  const int c = group_lane<DP>();
+  const int64_t w = group_index<DP, int64_t>();
   const int B = a.batch, d = a.d, U = a.n_users, I = a.n_items, L = a.L;
   const int64_t n_keys = (int64_t)B * (2 + L);
-  if (w >= n_keys) return;
-  const uint64_t key = a.d_keys[w];
-  if (key == kSentinel) return;
-  const uint32_t row = (uint32_t)(key >> 32);
-  if (w > 0 && (uint32_t)(a.d_keys[w - 1] >> 32) == row) return;            // not the head of its run
+  const int row = head_row(a.d_keys, n_keys, w);
+  if (row < 0) return;
   const float reg = a.reg;
-  const bool is_user = (int)row < U, is_target = !is_user && (int)row < U + I;
-  const int r = is_user ? (int)row : is_target ? (int)row - U : (int)row - U - I;
+  const bool is_user = row < U, is_target = !is_user && row < U + I;
+  const int r = is_user ? row : is_target ? row - U : row - U - I;
   const float* table = is_user ? a.d_P : is_target ? a.d_V : a.d_W;
   float* dst = is_user ? a.d_G_P : is_target ? a.d_G_V : a.d_G_W;
-  float own[CPL], acc[CPL];
-#pragma unroll
-  for (int k = 0; k < CPL; ++k) {
-    const int col = c + k * DP;
-    acc[k] = 0.f;
-    own[k] = col < d ? table[(int64_t)r * d + col] : 0.f;
-  }
-  for (int64_t q = w; q < n_keys; ++q) {
-    const uint64_t kk = a.d_keys[q];
-    if ((uint32_t)(kk >> 32) != row) break;
-    const uint32_t pos = (uint32_t)kk;
+  float own[CPL], acc[CPL] = {};
+  load_row<DP, CPL>(table, r, d, c, own);
+  for_run(a.d_keys, n_keys, w, row, [&](uint32_t pos) {
     if (is_user) {
       // the user's row: g relu(V[i]) where its own entry is positive
       const int t = (int)pos;
@@ -239,12 +183,8 @@ __global__ __launch_bounds__(256) void npe_rows_kernel(nrhip_npe_step_args a) {
         if (col < d) acc[k] += a.d_ds[(int64_t)t * d + col] + reg * own[k];
       }
     }
-  }
-#pragma unroll
-  for (int k = 0; k < CPL; ++k) {
-    const int col = c + k * DP;
-    if (col < d) dst[(int64_t)r * d + col] = acc[k];
-  }
+  });
+  store_row<DP, CPL>(dst, r, d, c, acc);
 }
 
 template <int DP, int CPL>
@@ -253,9 +193,7 @@ __global__ __launch_bounds__(256) void npe_factors_kernel(const float* __restric
                                                           const int32_t* __restrict__ last,
                                                           const int32_t* __restrict__ users, int batch,
                                                           float* __restrict__ out, int64_t ld) {
-  constexpr int G = NR_WAVE / DP;
-  const int lane = threadIdx.x & 63, c = lane % DP;
-  const int b = (blockIdx.x * 4 + (threadIdx.x >> 6)) * G + lane / DP;
+  const int c = group_lane<DP>(), b = group_index<DP>();
   if (b >= batch) return;
   const int u = users ? users[b] : b;
   float s[CPL], sq = 0.f;
@@ -276,15 +214,6 @@ __global__ __launch_bounds__(256) void npe_relu_kernel(const float* __restrict__
 
 }  // namespace
 
-// lane groups sized to d: KERNEL<lanes per row, columns per lane>
-#define NR_NPE_BY_WIDTH(KERNEL, d, groups, st, ...)                                                                    \
-  do {                                                                                                                 \
-    if ((d) <= 16) hipLaunchKernelGGL((KERNEL<16, 1>), dim3((unsigned)(((groups) + 15) / 16)), dim3(256), 0, st, __VA_ARGS__);    \
-    else if ((d) <= 32) hipLaunchKernelGGL((KERNEL<32, 1>), dim3((unsigned)(((groups) + 7) / 8)), dim3(256), 0, st, __VA_ARGS__); \
-    else if ((d) <= 64) hipLaunchKernelGGL((KERNEL<64, 1>), dim3((unsigned)(((groups) + 3) / 4)), dim3(256), 0, st, __VA_ARGS__); \
-    else hipLaunchKernelGGL((KERNEL<64, 2>), dim3((unsigned)(((groups) + 3) / 4)), dim3(256), 0, st, __VA_ARGS__);                \
-  } while (0)
-
 extern "C" {
 
 int nrhip_npe_step(const nrhip_npe_step_args* args, void* stream) {
@@ -300,20 +229,19 @@ int nrhip_npe_step(const nrhip_npe_step_args* args, void* stream) {
   NR_REQUIRE(a.batch >= 0 && a.batch <= NRHIP_NPE_MAX_BATCH && a.n_users >= 0 && a.n_items >= 0 &&
                  (int64_t)a.n_users + 2 * (int64_t)a.n_items < ((int64_t)1 << 31) - 1, NR_ERR_ARG,
              "npe_step: bad sizes (batch 0..%d, n_users + 2 n_items < 2^31 - 1)", NRHIP_NPE_MAX_BATCH);
-  NR_REQUIRE(a.loss_kind == nr::NR_POINT_CROSS_ENTROPY || a.loss_kind == nr::NR_POINT_SQUARE, NR_ERR_ARG,
-             "npe_step: unknown pointwise loss %d (0 cross_entropy, 1 square)", a.loss_kind);
+  NR_TRY(check_loss_kind("npe_step", 0, a.loss_kind));
   hipStream_t st = (hipStream_t)stream;
   const int B = a.batch;
   const int64_t n_keys = (int64_t)B * (2 + a.L);
   if (B > 0) {
-    NR_NPE_BY_WIDTH(npe_forward_kernel, a.d, (int64_t)B, st, a);
+    NR_BY_WIDTH(npe_forward_kernel, a.d, B, st, a);
     NR_LAUNCH_CHECK();
     NR_TRY(nrhip_sort_u64(a.d_keys, (int)n_keys, stream));
   }
-  hipLaunchKernelGGL(npe_loss_kernel, dim3(1), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(loss_kernel<nrhip_npe_step_args>, dim3(1), dim3(256), 0, st, a);
   NR_LAUNCH_CHECK();
   if (B > 0) {
-    NR_NPE_BY_WIDTH(npe_rows_kernel, a.d, n_keys, st, a);
+    NR_BY_WIDTH(npe_rows_kernel, a.d, n_keys, st, a);
     NR_LAUNCH_CHECK();
   }
   return NR_OK;
@@ -330,7 +258,7 @@ int nrhip_npe_user_factors(const float* d_P, const float* d_W, int n_users, int 
                  (d_users || batch <= n_users), NR_ERR_ARG, "npe_user_factors: bad arguments");
   if (batch == 0) return NR_OK;
   hipStream_t st = (hipStream_t)stream;
-  NR_NPE_BY_WIDTH(npe_factors_kernel, d, (int64_t)batch, st, d_P, d_W, n_users, n_items, d, L, d_last, d_users, batch,
+  NR_BY_WIDTH(npe_factors_kernel, d, batch, st, d_P, d_W, n_users, n_items, d, L, d_last, d_users, batch,
                   d_out, ld);
   NR_LAUNCH_CHECK();
   return NR_OK;

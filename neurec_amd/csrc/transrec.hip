@@ -41,18 +41,17 @@
 //                             threads read 64 consecutive floats, the 4 rows of a wavefront broadcast)
 //
 // Every float sum is taken in a fixed order and nothing is accumulated with atomics: two runs are bit-identical.
-#include "nr_common.h"
+#include "rowkey_common.h"
 #include "neurec_hip.h"
 
 namespace {
 
-constexpr uint64_t kSentinel = 0x7fffffffffffffffull;     // a slot that takes no part sorts behind every key
-constexpr int kScal = 4;                                  // floats per batch slot in d_scal
-enum { S_G = 0, S_LOSS = 1, S_L2 = 2, S_OK = 3 };
+using namespace nr::rowkey;
+
 enum { ROLE_RECENT = 0, ROLE_TARGET = 1, ROLE_NEGATIVE = 2 };
 
 __device__ __forceinline__ uint64_t row_key(int row, int pos, int role) {
-  return ((uint64_t)(uint32_t)row << 32) | ((uint32_t)pos << 2) | (uint32_t)role;
+  return nr::rowkey::row_key(row, ((uint32_t)pos << 2) | (uint32_t)role);
 }
 
 __host__ __device__ inline int chunks_of(int B) {
@@ -62,9 +61,7 @@ __host__ __device__ inline int chunks_of(int B) {
 
 template <int DP, int CPL>
 __global__ __launch_bounds__(256) void transrec_forward_kernel(nrhip_transrec_step_args a) {
-  constexpr int G = NR_WAVE / DP;
-  const int lane = threadIdx.x & 63, c = lane % DP;
-  const int t = (blockIdx.x * 4 + (threadIdx.x >> 6)) * G + lane / DP;
+  const int c = group_lane<DP>(), t = group_index<DP>();
   const int B = a.batch, d = a.d, U = a.n_users, I = a.n_items;
   const int N = a.pairwise ? 2 * B : B;
   const bool in = t < B;
@@ -98,32 +95,20 @@ __global__ __launch_bounds__(256) void transrec_forward_kernel(nrhip_transrec_st
       }
     }
   }
-  // groups are DP-aligned: the xor partners of a lane are lanes of its own group
-#pragma unroll
-  for (int m = DP / 2; m >= 1; m >>= 1) {
-    si += __shfl_xor(si, m, NR_WAVE);
-    sj += __shfl_xor(sj, m, NR_WAVE);
-    sq += __shfl_xor(sq, m, NR_WAVE);
-  }
+  group_sum<DP>(si, sj, sq);
   if (!in || c != 0) return;
   float g = 0.f, loss = 0.f;
   if (ok) {
     const float bi = a.d_b[i];
     const float xi = bi - si;
+    float xj = 0.f;
     sq += bi * bi;
     if (a.pairwise) {
       const float bj = a.d_b[j];
-      const float y = xi - (bj - sj);
+      xj = bj - sj;
       sq += bj * bj;
-      loss = nr::pairwise_loss(a.loss_kind, y);
-      g = nr::pairwise_dloss(a.loss_kind, y);
-    } else {
-      // tf.losses.sigmoid_cross_entropy is a MEAN over the batch, every other loss of util/learner.py a sum
-      const float scale = a.loss_kind == nr::NR_POINT_CROSS_ENTROPY ? 1.0f / (float)B : 1.0f;
-      const float z = ((const float*)a.d_third)[t];
-      loss = scale * nr::pointwise_loss(a.loss_kind, z, xi);
-      g = scale * nr::pointwise_dloss(a.loss_kind, z, xi);
     }
+    instance_loss_g(a.pairwise, a.loss_kind, B, a.d_third, t, xi, xj, loss, g);
     if (a.d_flag_P) a.d_flag_P[u] = 1;
     if (a.d_flag_Q) {
       a.d_flag_Q[l] = 1;
@@ -136,9 +121,7 @@ __global__ __launch_bounds__(256) void transrec_forward_kernel(nrhip_transrec_st
     }
   }
   float* sc = a.d_scal + (int64_t)t * kScal;
-  sc[S_G] = g;
-  sc[S_LOSS] = loss;
-  sc[S_L2] = ok ? 0.5f * sq : 0.f;
+  store_slot(sc, g, loss, sq, ok);
   sc[S_OK] = ok ? 1.f : 0.f;
   a.d_keys[t] = ok ? row_key(u, t, ROLE_RECENT) : kSentinel;
   a.d_keys[N + t] = ok ? row_key(U + l, t, ROLE_RECENT) : kSentinel;
@@ -151,63 +134,37 @@ __global__ __launch_bounds__(256) void transrec_forward_kernel(nrhip_transrec_st
 }
 
 __global__ __launch_bounds__(256) void transrec_loss_kernel(nrhip_transrec_step_args a) {
-  __shared__ double s_a[256], s_b[256];
-  double la = 0.0, lb = 0.0;
-  for (int t = threadIdx.x; t < a.batch; t += 256) {
-    const float* sc = a.d_scal + (int64_t)t * kScal;
-    la += (double)sc[S_LOSS];
-    lb += (double)sc[S_L2];
-  }
+  double v[2] = {0.0, 0.0};
+  slot_sums(a.d_scal, a.batch, v[0], v[1]);
   // l2_loss(..., global_embedding): T enters once per step (TransRec.py:88,91)
-  for (int c = threadIdx.x; c < a.d; c += 256) lb += 0.5 * (double)a.d_T[c] * (double)a.d_T[c];
-  s_a[threadIdx.x] = la;
-  s_b[threadIdx.x] = lb;
-  __syncthreads();
-  for (int s = 128; s >= 1; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-      s_a[threadIdx.x] += s_a[threadIdx.x + s];
-      s_b[threadIdx.x] += s_b[threadIdx.x + s];
-    }
-    __syncthreads();
-  }
+  for (int c = threadIdx.x; c < a.d; c += 256) v[1] += 0.5 * (double)a.d_T[c] * (double)a.d_T[c];
+  block_sum(v);
   if (threadIdx.x == 0) {
-    a.d_loss2[0] = (float)s_a[0];
-    a.d_loss2[1] = (float)((double)a.reg * s_b[0]);
+    a.d_loss2[0] = (float)v[0];
+    a.d_loss2[1] = (float)((double)a.reg * v[1]);
   }
 }
 
 // the sum of one run of the sorted keys: the row's occurrences in key order, each recomputed from the gathered rows
 template <int DP, int CPL>
 __global__ __launch_bounds__(256) void transrec_rows_kernel(nrhip_transrec_step_args a) {
-  constexpr int G = NR_WAVE / DP;
-  const int lane = threadIdx.x & 63, c = lane % DP;
-  const int64_t w = (int64_t)(blockIdx.x * 4 + (threadIdx.x >> 6)) * G + lane / DP;
+  const int c = group_lane<DP>();
+  const int64_t w = group_index<DP, int64_t>();
   const int B = a.batch, d = a.d, U = a.n_users;
   const int64_t n_keys = 3 * (int64_t)(a.pairwise ? 2 * B : B);
-  if (w >= n_keys) return;
-  const uint64_t key = a.d_keys[w];
-  if (key == kSentinel) return;
-  const uint32_t row = (uint32_t)(key >> 32);
-  if (w > 0 && (uint32_t)(a.d_keys[w - 1] >> 32) == row) return;            // not the head of its run
+  const int row = head_row(a.d_keys, n_keys, w);
+  if (row < 0) return;
   const float reg = a.reg;
   const int32_t* negs = (const int32_t*)a.d_third;
-  const bool is_user = (int)row < U;
-  const int r = is_user ? (int)row : (int)row - U;
-  const float* own_table = is_user ? a.d_P : a.d_Q;
-  float own[CPL], acc[CPL];
-#pragma unroll
-  for (int k = 0; k < CPL; ++k) {
-    const int col = c + k * DP;
-    acc[k] = 0.f;
-    own[k] = col < d ? own_table[(int64_t)r * d + col] : 0.f;
-  }
+  const bool is_user = row < U;
+  const int r = is_user ? row : row - U;
+  float own[CPL], acc[CPL] = {};
+  load_row<DP, CPL>(is_user ? a.d_P : a.d_Q, r, d, c, own);
   float gb = 0.f;
   bool has_b = false;
   const float own_b = is_user ? 0.f : a.d_b[r];
-  for (int64_t q = w; q < n_keys; ++q) {
-    const uint64_t kk = a.d_keys[q];
-    if ((uint32_t)(kk >> 32) != row) break;
-    const int role = (int)((uint32_t)kk & 3u), pos = (int)((uint32_t)kk >> 2);
+  for_run(a.d_keys, n_keys, w, row, [&](uint32_t low) {
+    const int role = (int)(low & 3u), pos = (int)(low >> 2);
     const bool second = pos >= B;
     const int t = second ? pos - B : pos;
     const float g = a.d_scal[(int64_t)t * kScal + S_G];
@@ -234,13 +191,8 @@ __global__ __launch_bounds__(256) void transrec_rows_kernel(nrhip_transrec_step_
         acc[k] += with_reg ? s * v + reg * own[k] : s * v;
       }
     }
-  }
-  float* dst = is_user ? a.d_G_P : a.d_G_Q;
-#pragma unroll
-  for (int k = 0; k < CPL; ++k) {
-    const int col = c + k * DP;
-    if (col < d) dst[(int64_t)r * d + col] = acc[k];
-  }
+  });
+  store_row<DP, CPL>(is_user ? a.d_G_P : a.d_G_Q, r, d, c, acc);
   if (has_b && c == 0) a.d_G_b[r] = gb;                  // a run of recents alone leaves G_b[r] as it is
 }
 
@@ -353,15 +305,6 @@ __global__ __launch_bounds__(256) void transrec_scores_kernel(const float* __res
 
 }  // namespace
 
-// lane groups sized to d: KERNEL<lanes per row, columns per lane>
-#define NR_TRANSREC_BY_WIDTH(KERNEL, d, groups, st, ...)                                                      \
-  do {                                                                                                        \
-    if ((d) <= 16) hipLaunchKernelGGL((KERNEL<16, 1>), dim3(((groups) + 15) / 16), dim3(256), 0, st, __VA_ARGS__);      \
-    else if ((d) <= 32) hipLaunchKernelGGL((KERNEL<32, 1>), dim3(((groups) + 7) / 8), dim3(256), 0, st, __VA_ARGS__);   \
-    else if ((d) <= 64) hipLaunchKernelGGL((KERNEL<64, 1>), dim3(((groups) + 3) / 4), dim3(256), 0, st, __VA_ARGS__);   \
-    else hipLaunchKernelGGL((KERNEL<64, 2>), dim3(((groups) + 3) / 4), dim3(256), 0, st, __VA_ARGS__);                  \
-  } while (0)
-
 extern "C" {
 
 int nrhip_transrec_step(const nrhip_transrec_step_args* args, void* stream) {
@@ -372,12 +315,7 @@ int nrhip_transrec_step(const nrhip_transrec_step_args* args, void* stream) {
   NR_REQUIRE(a.batch >= 0 && a.batch <= NRHIP_TRANSREC_MAX_BATCH && a.n_users >= 0 && a.n_items >= 0 &&
                  (int64_t)a.n_users + (int64_t)a.n_items < ((int64_t)1 << 31) - 1, NR_ERR_ARG,
              "transrec_step: bad sizes");
-  if (a.pairwise)
-    NR_REQUIRE(a.loss_kind >= nr::NR_PAIR_BPR && a.loss_kind <= nr::NR_PAIR_SQUARE, NR_ERR_ARG,
-               "transrec_step: unknown pairwise loss %d (0 bpr, 1 hinge, 2 square)", a.loss_kind);
-  else
-    NR_REQUIRE(a.loss_kind == nr::NR_POINT_CROSS_ENTROPY || a.loss_kind == nr::NR_POINT_SQUARE, NR_ERR_ARG,
-               "transrec_step: unknown pointwise loss %d (0 cross_entropy, 1 square)", a.loss_kind);
+  NR_TRY(check_loss_kind("transrec_step", a.pairwise, a.loss_kind));
   const int B = a.batch;
   if (B == 0) return NR_OK;                                // no work: nothing is launched, nothing is written
   NR_REQUIRE(a.d_P && a.d_Q && a.d_b && a.d_T && a.d_G_P && a.d_G_Q && a.d_G_b && a.d_G_T && a.d_users && a.d_recent &&
@@ -385,12 +323,12 @@ int nrhip_transrec_step(const nrhip_transrec_step_args* args, void* stream) {
              "transrec_step: null pointer argument");
   hipStream_t st = (hipStream_t)stream;
   const int n_keys = 3 * B * (a.pairwise ? 2 : 1), chunks = chunks_of(B);
-  NR_TRANSREC_BY_WIDTH(transrec_forward_kernel, a.d, B, st, a);
+  NR_BY_WIDTH(transrec_forward_kernel, a.d, B, st, a);
   NR_LAUNCH_CHECK();
   NR_TRY(nrhip_sort_u64(a.d_keys, n_keys, stream));
   hipLaunchKernelGGL(transrec_loss_kernel, dim3(1), dim3(256), 0, st, a);
   NR_LAUNCH_CHECK();
-  NR_TRANSREC_BY_WIDTH(transrec_rows_kernel, a.d, n_keys, st, a);
+  NR_BY_WIDTH(transrec_rows_kernel, a.d, n_keys, st, a);
   NR_LAUNCH_CHECK();
   hipLaunchKernelGGL(transrec_gt_kernel, dim3(chunks), dim3(NRHIP_TRANSREC_MAX_D), 0, st, a, chunks);
   NR_LAUNCH_CHECK();
