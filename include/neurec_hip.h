@@ -2007,6 +2007,96 @@ int nrhip_sasrec_step(const nrhip_sasrec_step_args* args, void* stream);
 int nrhip_sasrec_forward(const nrhip_sasrec_weights* weights, const int32_t* d_seq, int batch, float* d_ws, float scale,
                          float* d_out, int64_t ld, void* stream);
 
+/* ---- Caser (vertical and horizontal convolutions over the L x d window of a user's last items) ---------------------
+ * These symbols are additions: no existing struct changes and NRHIP_ABI_VERSION stays 4.
+ * nrhip_caser_step replaces one `sess.run(self.train_opt, feed_dict=feed)` of Caser.py:139 up to the optimiser: the
+ * graph of Caser.py:70-116 forward with training on, the loss and every gradient.  d_users int32 [batch], d_seq
+ * [batch][L], d_pos [batch][T], d_neg [batch][N]; the padding item is id n_items (any id outside [0, n_items) reads a
+ * zero row, and its gradient is dropped).  F = nv d + nh L.
+ *     E = concat(seq_item, zeros[1, d])[seq]                                            [L][d]
+ *     feature[j nv + c]            = conv_v_bias[c] + sum_t E[t][j] conv_v[t][c]        (no activation)
+ *     feature[nv d + (i - 1) nh + c] = max_p relu(conv_h_bias[i][c] + sum_{t < i, j} E[p + t][j] conv_h[i][t][j][c]),
+ *                                    heights i = 1..L, positions p = 0..L - i; the first maximum takes the gradient
+ *     x = feature / (1 - rate) * mask;  z = relu(x fc + fc_bias);  p = concat(z, user[u])
+ *     logit_k = p . item[tar_k] + item_bias[tar_k], the T positives, then the N negatives; a pad target has logit 0
+ *     loss = mean_{batch T}(-log(sigmoid(pos) + 1e-24)) + mean_{batch N}(-log(1 - sigmoid(neg) + 1e-24))
+ *            (+ l2_reg (sum user^2 + sum seq_item^2 + sum item^2 + sum item_bias^2) / 2 when l2_reg != 0)
+ * written as the reference writes it, in fp32, with the sigmoid's derivative y (1 - y): a saturated term is exactly
+ * -log(1e-24) with gradient 0.
+ * Variables: d_user [U][d], d_seq_item [I][d], d_item [I][2 d], d_item_bias [I], d_conv_v [L][nv] (the Conv2D kernel
+ * [L][1][1][nv]), d_conv_v_bias [nv], d_conv_h[i - 1] [i][d][nh] (the kernel [i][d][1][nh]), d_conv_h_bias[i - 1] [nh],
+ * d_fc [F][d], d_fc_bias [d].
+ * Dropout: d_mask != NULL is the uint8 {0, 1} keep mask [batch][F]; otherwise a counter-based generator keyed by (seed,
+ * step, element).  rate 0 applies none.
+ * Output: d_loss2[0] the loss term, d_loss2[1] the regulariser term; every gradient STORED (the four tables' buffers must
+ * be zero on entry: only the rows the batch touches are written, a row that occurs in several slots as the sum of its
+ * slots in slot order, plus l2_reg v on every row when l2_reg != 0; the conv and dense gradients are stored whole).
+ * Work buffers: d_keys uint64 [batch (1 + L + T + N)]; d_ws float [nrhip_caser_workspace_floats].
+ * Limits: factors_num 1..NRHIP_CASER_MAX_WIDTH, seq_L 1..NRHIP_CASER_MAX_LEN, nv 1..NRHIP_CASER_MAX_NV, nh
+ * 1..NRHIP_CASER_MAX_NH, seq_T and neg_samples 1..NRHIP_CASER_MAX_TARGETS, batch 0..NRHIP_CASER_MAX_BATCH, n_users +
+ * 2 n_items < 2^31 (the rows of one sort-key space); outside: NRHIP_ERR_UNSUPPORTED.  batch == 0 launches nothing and
+ * writes nothing.  fp32 throughout (the reported sums are added in double and rounded once), every sum in a fixed
+ * order, no atomics: two calls on the same inputs are bit-identical. */
+#define NRHIP_CASER_MAX_WIDTH 128
+#define NRHIP_CASER_MAX_LEN 10
+#define NRHIP_CASER_MAX_NV 16
+#define NRHIP_CASER_MAX_NH 64
+#define NRHIP_CASER_MAX_TARGETS 16
+#define NRHIP_CASER_MAX_BATCH 4096
+typedef struct nrhip_caser_weights {
+  const float* d_user;
+  const float* d_seq_item;
+  const float* d_item;
+  const float* d_item_bias;
+  const float* d_conv_v;
+  const float* d_conv_v_bias;
+  const float* d_conv_h[NRHIP_CASER_MAX_LEN];
+  const float* d_conv_h_bias[NRHIP_CASER_MAX_LEN];
+  const float* d_fc;
+  const float* d_fc_bias;
+  int n_users, n_items, d, L, nv, nh;
+} nrhip_caser_weights;
+typedef struct nrhip_caser_step_args {
+  nrhip_caser_weights w;
+  float* d_G_user;
+  float* d_G_seq_item;
+  float* d_G_item;
+  float* d_G_item_bias;
+  float* d_G_conv_v;
+  float* d_G_conv_v_bias;
+  float* d_G_conv_h[NRHIP_CASER_MAX_LEN];
+  float* d_G_conv_h_bias[NRHIP_CASER_MAX_LEN];
+  float* d_G_fc;
+  float* d_G_fc_bias;
+  const int32_t* d_users;
+  const int32_t* d_seq;
+  const int32_t* d_pos;
+  const int32_t* d_neg;
+  const uint8_t* d_mask;
+  uint64_t* d_keys;
+  float* d_ws;
+  float* d_loss2;
+  uint64_t seed;
+  int batch, T, N, step;
+  float rate, l2_reg;
+} nrhip_caser_step_args;
+/* Replaces the storage TensorFlow gives the intermediate tensors of the graph and their gradients: the size in floats
+ * of nrhip_caser_step's d_ws for batches up to max_batch. */
+int nrhip_caser_workspace_floats(int max_batch, int seq_L, int factors_num, int nv, int nh, int seq_T, int neg_samples,
+                                 size_t* floats);
+/* Replaces one `sess.run(self.train_opt, feed_dict=feed)` of Caser.py:139 up to the optimiser; the head of this section
+ * has the graph, the outputs and the limits. */
+int nrhip_caser_step(const nrhip_caser_step_args* args, void* stream);
+/* Replaces the forward half of `sess.run(self.all_logits, ...)` of Caser.py:202: the graph with training off on d_users
+ * [n] and d_seq [n][L]; d_out[b][0..2 d) = concat(z, user[u]) (row stride ld).  d_ws is not read (the pass keeps a row
+ * in LDS) and may be NULL. */
+int nrhip_caser_forward(const nrhip_caser_weights* weights, const int32_t* d_users, const int32_t* d_seq, int n,
+                        float* d_ws, float* d_out, int64_t ld, void* stream);
+/* Replaces the matmul of `self.all_logits` (Caser.py:122) for rows wider than nrhip_gru4rec_scores takes (2 d > 128):
+ * d_out[r][i] = d_H[r][0..width) . d_Q[i][0..width), no bias; width 1..2 NRHIP_CASER_MAX_WIDTH. */
+int nrhip_caser_scores(const float* d_H, int64_t ldh, const float* d_Q, int n, int n_items, int width, float* d_out,
+                       int64_t ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

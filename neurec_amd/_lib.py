@@ -274,6 +274,27 @@ class SasrecStepArgs(C.Structure):
                 ("seed", C.c_uint64), ("batch", C.c_int), ("step", C.c_int), ("rate", C.c_float), ("l2_emb", C.c_float)]
 
 
+CASER_MAX_LEN = 10
+
+
+class CaserWeights(C.Structure):
+    """nrhip_caser_weights (include/neurec_hip.h)"""
+    _fields_ = [(n, C.c_void_p) for n in ("user", "seq_item", "item", "item_bias", "conv_v", "conv_v_bias")] + \
+        [("conv_h", C.c_void_p * CASER_MAX_LEN), ("conv_h_bias", C.c_void_p * CASER_MAX_LEN), ("fc", C.c_void_p),
+         ("fc_bias", C.c_void_p)] + [(n, C.c_int) for n in ("n_users", "n_items", "d", "L", "nv", "nh")]
+
+
+class CaserStepArgs(C.Structure):
+    """nrhip_caser_step_args (include/neurec_hip.h)"""
+    _fields_ = [("w", CaserWeights)] + \
+        [(n, C.c_void_p) for n in ("G_user", "G_seq_item", "G_item", "G_item_bias", "G_conv_v", "G_conv_v_bias")] + \
+        [("G_conv_h", C.c_void_p * CASER_MAX_LEN), ("G_conv_h_bias", C.c_void_p * CASER_MAX_LEN), ("G_fc", C.c_void_p),
+         ("G_fc_bias", C.c_void_p)] + \
+        [(n, C.c_void_p) for n in ("users", "seq", "pos", "neg", "mask", "keys", "ws", "loss2")] + \
+        [("seed", C.c_uint64), ("batch", C.c_int), ("T", C.c_int), ("N", C.c_int), ("step", C.c_int),
+         ("rate", C.c_float), ("l2_reg", C.c_float)]
+
+
 # name -> argtypes; every function returns int status except where noted.
 SIGNATURES = {
     "nrhip_device_info": [C.POINTER(i32), C.POINTER(i32), psz, C.c_char_p, i32],
@@ -489,6 +510,10 @@ SIGNATURES = {
     "nrhip_sasrec_workspace_floats": [i32, i32, i32, i32, i32, psz],
     "nrhip_sasrec_step": [C.POINTER(SasrecStepArgs), p],
     "nrhip_sasrec_forward": [C.POINTER(SasrecWeights), p, i32, p, C.c_float, p, i64, p],
+    "nrhip_caser_workspace_floats": [i32, i32, i32, i32, i32, i32, i32, psz],
+    "nrhip_caser_step": [C.POINTER(CaserStepArgs), p],
+    "nrhip_caser_forward": [C.POINTER(CaserWeights), p, p, i32, p, p, i64, p],
+    "nrhip_caser_scores": [p, i64, p, i32, i32, i32, p, i64, p],
 }
 
 for _name, _args in SIGNATURES.items():

@@ -60,6 +60,8 @@ MODELS = {
                     ("sample_alpha", "0.75"), ("epochs", "1000")],
     "SASRec": [("lr", "0.001"), ("l2_emb", "0.0"), ("hidden_units", "50"), ("dropout_rate", "0.5"), ("max_len", "50"),
                ("num_blocks", "2"), ("num_heads", "1"), ("batch_size", "128"), ("epochs", "1000")],
+    "Caser": [("lr", "0.001"), ("l2_reg", "0.001"), ("factors_num", "50"), ("seq_L", "5"), ("seq_T", "3"), ("nv", "4"),
+              ("nh", "16"), ("dropout", "0.5"), ("neg_samples", "3"), ("batch_size", "256"), ("epochs", "1000")],
 }
 
 
