@@ -2097,6 +2097,105 @@ int nrhip_caser_forward(const nrhip_caser_weights* weights, const int32_t* d_use
 int nrhip_caser_scores(const float* d_H, int64_t ldh, const float* d_Q, int n, int n_items, int width, float* d_out,
                        int64_t ld, void* stream);
 
+/* ---- SRGNN (a gated graph network over each session's item graph, attention readout, full softmax) ---------------
+ * These symbols are additions: no existing struct changes and NRHIP_ABI_VERSION stays 4.
+ * nrhip_srgnn_step replaces one `sess.run(self.train_opt, feed_dict=feed)` of SRGNN.py:162 up to the optimiser: the
+ * session graphs of SRGNN.py:176-205, the graph of SRGNN.py:75-136 forward, the loss and all 14 gradients.  d is
+ * hidden_size, I num_items, L max_seq_len.
+ * The feed, one of two forms (nrhip_srgnn_feed):
+ *     d_seq int32 [batch][L] post-padded with id I — the first id outside [0, I) ends the session — and d_target
+ *     int32 [batch]; or
+ *     d_users, d_ends int32 [batch] over resident sequences (d_seq_ptr int64 [n_users + 1], d_seq_flat int32): the
+ *     session is the last L of user u's first `end` items and the target the item at `end` (none when end is the
+ *     user's item count: the forward pass).  A user or an end outside the data gives the empty session.
+ * Per session, with items s_0 .. s_{len-1}:
+ *     nodes = the distinct items ascending; alias[t] = the node of s_t; adj[alias[t]][alias[t + 1]] = 1
+ *     A_in[i][j] = adj[i][j] / max(colsum_j, 1);  A_out[i][j] = adj[j][i] / max(rowsum_j, 1)   (both divisors by j)
+ *     h = embedding[nodes];  `step` times:  x = [A_in (h W_in + b_in), A_out (h W_out + b_out)]
+ *         [r, u] = sigmoid([x, h] gates_kernel + gates_bias);  c = tanh([x, r * h] candidate_kernel + candidate_bias)
+ *         h = u h + (1 - u) c                                   (the gradient flows through the state h)
+ *     last = h[alias[len - 1]] nasr_w1;  m_t = sigmoid(last + h[alias[t]] nasr_w2 + nasr_b)
+ *     a = sum_t (m_t . nasrv) h[alias[t]];  sess = [a, last] B, or a when nonhybrid
+ *     logits = sess . embedding^T [I];  loss = mean_b(log sum exp(logits - max) + max - logits[target])
+ *            + l2 (sum over all 14 variables of sum v^2) / 2
+ * The graph is never a dense n x n matrix: the distinct edges are two sorted lists with row pointers, and A_in . /
+ * A_out . walk a node's edges.  The empty session has sess = 0.  A target outside [0, I) takes its session out of the
+ * loss and the gradients (it stays in the mean's denominator).
+ * Variables: d_nasr_w1, d_nasr_w2, d_W_in, d_W_out [d][d]; d_nasrv, d_nasr_b, d_b_in, d_b_out [d]; d_embedding [I][d]
+ * (the pad row I is not stored and never written); d_B [2 d][d]; d_gates_kernel [3 d][2 d], d_gates_bias [2 d];
+ * d_candidate_kernel [3 d][d], d_candidate_bias [d].
+ * Output: d_loss2[0] the cross-entropy mean, d_loss2[1] the regulariser term; every gradient STORED whole (d_G_B is
+ * l2 B when nonhybrid), l2 v included.
+ * Work buffers: d_keys uint64 [batch L]; d_ws float [nrhip_srgnn_workspace_floats].
+ * Limits: hidden_size 1..NRHIP_SRGNN_MAX_WIDTH, max_seq_len 1..NRHIP_SRGNN_MAX_LEN, step 1..NRHIP_SRGNN_MAX_STEP,
+ * batch 0..NRHIP_SRGNN_MAX_BATCH, batch * num_items < 2^31; outside: NRHIP_ERR_UNSUPPORTED.  batch == 0 launches
+ * nothing and writes nothing.  fp32 throughout (the reported sums are added in double and rounded once), every sum in
+ * a fixed order, no atomics: two calls on the same inputs are bit-identical. */
+#define NRHIP_SRGNN_MAX_WIDTH 128
+#define NRHIP_SRGNN_MAX_LEN 256
+#define NRHIP_SRGNN_MAX_STEP 4
+#define NRHIP_SRGNN_MAX_BATCH 4096
+typedef struct nrhip_srgnn_weights {
+  const float* d_nasr_w1;
+  const float* d_nasr_w2;
+  const float* d_nasrv;
+  const float* d_nasr_b;
+  const float* d_embedding;
+  const float* d_W_in;
+  const float* d_b_in;
+  const float* d_W_out;
+  const float* d_b_out;
+  const float* d_B;
+  const float* d_gates_kernel;
+  const float* d_gates_bias;
+  const float* d_candidate_kernel;
+  const float* d_candidate_bias;
+  int n_items, d, L, step, nonhybrid;
+} nrhip_srgnn_weights;
+typedef struct nrhip_srgnn_feed {
+  const int32_t* d_seq;
+  const int32_t* d_target;
+  const int32_t* d_users;
+  const int32_t* d_ends;
+  const int64_t* d_seq_ptr;
+  const int32_t* d_seq_flat;
+  int n_users;
+} nrhip_srgnn_feed;
+typedef struct nrhip_srgnn_step_args {
+  nrhip_srgnn_weights w;
+  nrhip_srgnn_feed f;
+  float* d_G_nasr_w1;
+  float* d_G_nasr_w2;
+  float* d_G_nasrv;
+  float* d_G_nasr_b;
+  float* d_G_embedding;
+  float* d_G_W_in;
+  float* d_G_b_in;
+  float* d_G_W_out;
+  float* d_G_b_out;
+  float* d_G_B;
+  float* d_G_gates_kernel;
+  float* d_G_gates_bias;
+  float* d_G_candidate_kernel;
+  float* d_G_candidate_bias;
+  uint64_t* d_keys;
+  float* d_ws;
+  float* d_loss2;
+  int batch;
+  float l2;
+} nrhip_srgnn_step_args;
+/* Replaces the storage TensorFlow gives the intermediate tensors of the graph and their gradients, the [batch][I]
+ * logits included: the size in floats of d_ws for batches up to max_batch (nrhip_srgnn_forward needs no more). */
+int nrhip_srgnn_workspace_floats(int max_batch, int max_seq_len, int hidden_size, int step, int num_items,
+                                 size_t* floats);
+/* Replaces one `sess.run(self.train_opt, feed_dict=feed)` of SRGNN.py:162 up to the optimiser; the head of this
+ * section has the graph, the outputs and the limits. */
+int nrhip_srgnn_step(const nrhip_srgnn_step_args* args, void* stream);
+/* Replaces the forward half of `sess.run(self.all_logits, ...)` of SRGNN.py:230: d_out[b][0..d) = sess_b (row stride
+ * ld) for the n sessions of `feed` (its d_target is not read), with the kernels of the step. */
+int nrhip_srgnn_forward(const nrhip_srgnn_weights* weights, const nrhip_srgnn_feed* feed, int n, float* d_ws,
+                        float* d_out, int64_t ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

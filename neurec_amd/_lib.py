@@ -295,6 +295,28 @@ class CaserStepArgs(C.Structure):
          ("rate", C.c_float), ("l2_reg", C.c_float)]
 
 
+SRGNN_VARS = ("nasr_w1", "nasr_w2", "nasrv", "nasr_b", "embedding", "W_in", "b_in", "W_out", "b_out", "B", "gates_kernel",
+              "gates_bias", "candidate_kernel", "candidate_bias")
+
+
+class SrgnnWeights(C.Structure):
+    """nrhip_srgnn_weights (include/neurec_hip.h)"""
+    _fields_ = [(n, C.c_void_p) for n in SRGNN_VARS] + \
+        [(n, C.c_int) for n in ("n_items", "d", "L", "step", "nonhybrid")]
+
+
+class SrgnnFeed(C.Structure):
+    """nrhip_srgnn_feed (include/neurec_hip.h)"""
+    _fields_ = [(n, C.c_void_p) for n in ("seq", "target", "users", "ends", "seq_ptr", "seq_flat")] + \
+        [("n_users", C.c_int)]
+
+
+class SrgnnStepArgs(C.Structure):
+    """nrhip_srgnn_step_args (include/neurec_hip.h)"""
+    _fields_ = [("w", SrgnnWeights), ("f", SrgnnFeed)] + [("G_" + n, C.c_void_p) for n in SRGNN_VARS] + \
+        [(n, C.c_void_p) for n in ("keys", "ws", "loss2")] + [("batch", C.c_int), ("l2", C.c_float)]
+
+
 # name -> argtypes; every function returns int status except where noted.
 SIGNATURES = {
     "nrhip_device_info": [C.POINTER(i32), C.POINTER(i32), psz, C.c_char_p, i32],
@@ -514,6 +536,9 @@ SIGNATURES = {
     "nrhip_caser_step": [C.POINTER(CaserStepArgs), p],
     "nrhip_caser_forward": [C.POINTER(CaserWeights), p, p, i32, p, p, i64, p],
     "nrhip_caser_scores": [p, i64, p, i32, i32, i32, p, i64, p],
+    "nrhip_srgnn_workspace_floats": [i32, i32, i32, i32, i32, psz],
+    "nrhip_srgnn_step": [C.POINTER(SrgnnStepArgs), p],
+    "nrhip_srgnn_forward": [C.POINTER(SrgnnWeights), C.POINTER(SrgnnFeed), i32, p, p, i64, p],
 }
 
 for _name, _args in SIGNATURES.items():

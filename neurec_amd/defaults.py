@@ -62,6 +62,8 @@ MODELS = {
                ("num_blocks", "2"), ("num_heads", "1"), ("batch_size", "128"), ("epochs", "1000")],
     "Caser": [("lr", "0.001"), ("l2_reg", "0.001"), ("factors_num", "50"), ("seq_L", "5"), ("seq_T", "3"), ("nv", "4"),
               ("nh", "16"), ("dropout", "0.5"), ("neg_samples", "3"), ("batch_size", "256"), ("epochs", "1000")],
+    "SRGNN": [("lr", "0.001"), ("L2", "1e-5"), ("hidden_size", "64"), ("batch_size", "100"), ("epochs", "500"),
+              ("lr_dc", "0.1"), ("lr_dc_step", "3"), ("step", "1"), ("nonhybrid", "False"), ("max_seq_len", "200")],
 }
 
 
