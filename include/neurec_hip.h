@@ -922,7 +922,11 @@ int nrhip_sort_u64(uint64_t* d_keys, int n, void* stream);
  *                       class*G + d_size_off[source rank] + position) of the n rows it was asked for (ordered by
  *                       source rank, d_recv_prefix[world+1] their offsets) and d_index_of_pos[position] = index of
  *                       that occurrence among the n — the inputs of nrhip_rows_sum_sorted, which then adds the
- *                       returning gradient rows in the order TF's unsorted_segment_sum walks the concatenated batch. */
+ *                       returning gradient rows in the order TF's unsorted_segment_sum walks the concatenated batch.
+ * Nothing to route is a valid call: with batch == 0 nrhip_route_batch takes NULL for the three id arrays and for
+ * d_keys / d_packed / d_order / d_inv, touches none of them and still ZEROES d_counts (an empty batch asks every owner
+ * for nothing); with n == 0 nrhip_route_owner_keys takes NULL for d_rows / d_codes / d_keys_out and writes nothing, and
+ * nrhip_rows_sum_sorted / nrhip_rows_sum_sorted2 take NULL for d_sorted_keys and the d_src arrays and write nothing. */
 int nrhip_route_batch(const int32_t* d_users, const int32_t* d_pos, const int32_t* d_neg, int batch, int n_users,
                       int bu, int bi, int code_base, uint64_t* d_keys, int32_t* d_packed, int32_t* d_order,
                       int32_t* d_inv, int32_t* d_counts, int world, void* stream);

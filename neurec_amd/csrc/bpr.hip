@@ -1331,7 +1331,7 @@ static int rows_sum_sorted_launch(const uint64_t* d_sorted_keys, int n, const in
 
 int nrhip_rows_sum_sorted(const uint64_t* d_sorted_keys, int n, const int32_t* d_index_of_pos, int d,
                           const float* d_src, int64_t ld_src, float* d_dst, void* stream) {
-  NR_REQUIRE(d_sorted_keys && d_index_of_pos && d_src && d_dst && n >= 0 && d >= 1 && d <= 256 &&
+  NR_REQUIRE((n == 0 || (d_sorted_keys && d_src)) && d_index_of_pos && d_dst && n >= 0 && d >= 1 && d <= 256 &&
                  ld_src >= d, NR_ERR_ARG, "rows_sum_sorted: bad arguments");
   return rows_sum_sorted_launch(d_sorted_keys, n, d_index_of_pos, d, d_src, ld_src, d_dst, nullptr, 0, nullptr, stream);
 }
@@ -1340,8 +1340,8 @@ int nrhip_rows_sum_sorted(const uint64_t* d_sorted_keys, int n, const int32_t* d
 int nrhip_rows_sum_sorted2(const uint64_t* d_sorted_keys, int n, const int32_t* d_index_of_pos, int d,
                            const float* d_src_a, int64_t ld_a, float* d_dst_a, const float* d_src_b, int64_t ld_b,
                            float* d_dst_b, void* stream) {
-  NR_REQUIRE(d_sorted_keys && d_index_of_pos && d_src_a && d_dst_a && d_src_b && d_dst_b && n >= 0 && d >= 1 &&
-                 d <= 256 && ld_a >= d && ld_b >= d, NR_ERR_ARG, "rows_sum_sorted2: bad arguments");
+  NR_REQUIRE((n == 0 || (d_sorted_keys && d_src_a && d_src_b)) && d_index_of_pos && d_dst_a && d_dst_b && n >= 0 &&
+                 d >= 1 && d <= 256 && ld_a >= d && ld_b >= d, NR_ERR_ARG, "rows_sum_sorted2: bad arguments");
   return rows_sum_sorted_launch(d_sorted_keys, n, d_index_of_pos, d, d_src_a, ld_a, d_dst_a, d_src_b, ld_b, d_dst_b,
                                 stream);
 }

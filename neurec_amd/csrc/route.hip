@@ -154,11 +154,13 @@ extern "C" {
 int nrhip_route_batch(const int32_t* d_users, const int32_t* d_pos, const int32_t* d_neg, int batch, int n_users,
                       int bu, int bi, int code_base, uint64_t* d_keys, int32_t* d_packed, int32_t* d_order,
                       int32_t* d_inv, int32_t* d_counts, int world, void* stream) {
-  NR_REQUIRE(d_users && d_pos && d_neg && d_keys && d_packed && d_order && d_inv && batch >= 0 && n_users >= 0 &&
-                 bu >= 1 && bi >= 1 && code_base > batch && world >= 1, NR_ERR_ARG, "route_batch: bad arguments");
-  if (batch == 0) return NR_OK;
+  NR_REQUIRE((batch == 0 || (d_users && d_pos && d_neg && d_keys && d_packed && d_order && d_inv)) && batch >= 0 &&
+                 n_users >= 0 && bu >= 1 && bi >= 1 && code_base > batch && world >= 1, NR_ERR_ARG,
+             "route_batch: bad arguments");
   hipStream_t st = (hipStream_t)stream;
+  // an empty batch still asks every owner for nothing: the counts of the batch before must not survive it
   if (d_counts) NR_CHECK_HIP(hipMemsetAsync(d_counts, 0, sizeof(int32_t) * world, st));
+  if (batch == 0) return NR_OK;
   const dim3 grid((3 * batch + 255) / 256), block(256);
   hipLaunchKernelGGL(route_keys_kernel, grid, block, 0, st, d_users, d_pos, d_neg, batch, n_users, bu, bi, d_keys,
                      d_counts);
@@ -173,8 +175,8 @@ int nrhip_route_batch(const int32_t* d_users, const int32_t* d_pos, const int32_
 int nrhip_route_owner_keys(const int32_t* d_rows, const int32_t* d_codes, int n, const int32_t* d_recv_prefix,
                            const int32_t* d_size_off, int world, int global_batch, int code_base,
                            uint64_t* d_keys_out, int32_t* d_index_of_pos, void* stream) {
-  NR_REQUIRE(d_recv_prefix && d_size_off && d_keys_out && d_index_of_pos && n >= 0 && world >= 1 &&
-                 global_batch >= 0 && code_base > 0 && (n == 0 || (d_rows && d_codes)),
+  NR_REQUIRE(d_recv_prefix && d_size_off && d_index_of_pos && n >= 0 && world >= 1 &&
+                 global_batch >= 0 && code_base > 0 && (n == 0 || (d_rows && d_codes && d_keys_out)),
              NR_ERR_ARG, "route_owner_keys: bad arguments");
   if (n == 0) return NR_OK;
   hipLaunchKernelGGL(route_owner_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_rows,

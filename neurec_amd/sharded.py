@@ -122,7 +122,8 @@ class RowRouter:
         """The routing of EVERY batch of the planned stream, built by a handful of launches that work on all batches
         at once (csrc/route.hip: nrhip_route_epoch, nrhip_route_epoch_owner_keys; one all-to-all of the whole
         epoch's (row, code) pairs): afterwards a planned step issues NO routing launch — `planned_route(k)` hands out
-        slices.  Per batch the tables equal what `request` + `ordered_keys` compute (tests/test_sharded_gpu.py)."""
+        slices.  Per batch the tables equal what `request` + `ordered_keys` compute (tests/test_sharded_gpu.py; at
+        any world size against a numpy statement of the routing: tests/test_routing_gpu.py)."""
         users, pos, neg = classes
         dev, W, B = users.device, self.world, batch
         n, nb = users.numel(), send.shape[0]
@@ -228,7 +229,9 @@ class RowRouter:
     # ---- one batch
     def request(self, users, pos, neg, n_users, planned=None):
         """ids of one batch -> a Route: the requests in owner order went out, `asked` / `asked_code` are what this
-        rank was asked for.  planned = epoch_counts(k, B) or None (then counted now: one host sync)."""
+        rank was asked for.  planned = epoch_counts(k, B) or None (then counted now: one host sync).
+        A rank whose batch is empty (the short last batch has fewer triplets than ranks) sends nothing — the native
+        call zeroes the counts — and is still asked for the rows it owns: its recv_counts come from the exchange."""
         B = users.numel()
         n = 3 * B
         counts = None if planned is not None else self._counts
