@@ -2200,6 +2200,81 @@ int nrhip_srgnn_step(const nrhip_srgnn_step_args* args, void* stream);
 int nrhip_srgnn_forward(const nrhip_srgnn_weights* weights, const nrhip_srgnn_feed* feed, int n, float* d_ws,
                         float* d_out, int64_t ld, void* stream);
 
+/* ---- NeuMF / MLP (a relu layer stack over the concat of a user and an item row, plus a GMF dot product) -------------
+ * These symbols are additions: no existing struct changes and NRHIP_ABI_VERSION stays 4.
+ * nrhip_neumf_step replaces one `sess.run((self.loss, self.optimizer), feed_dict)` of NeuMF.py:146 / MLP.py up to the
+ * optimiser, in pointwise mode.  d is embedding_size (0: MLP.py — no GMF branch, no mf_* tables), e = layers[0] / 2
+ * (integer), w[k] = layers[k], n_layers of them.  Per instance (u, i, label):
+ *     x = [mlp_user[u] | mlp_item[i]]  (2 e wide);  h_k = relu(h_{k-1} kernel_k + bias_k), h_{-1} = x
+ *     y = sum_c mf_user[u][c] mf_item[i][c] + sum_j h_last[j]            (no output layer, no sigmoid)
+ *     loss_kind 0: sigmoid cross-entropy of (label, y), the MEAN over the batch; 1: (label - y)^2, the sum
+ *     regulariser: reg_mf (|mf_user[u]|^2 + |mf_item[i]|^2) / 2 + reg_mlp (|mlp_user[u]|^2 + |mlp_item[i]|^2) / 2 per
+ *     instance — on the gathered rows: a row the batch holds twice counts twice
+ * relu's gradient is 0 where the pre-activation is <= 0.  An instance with an id outside its table takes no part.
+ * Variables: d_mf_user [U][d], d_mf_item [I][d], d_mlp_user [U][e], d_mlp_item [I][e]; d_kernel[k] [in_k][w_k] with
+ * in_0 = 2 e and in_k = w_{k-1}; d_bias[k] [w_k].  A table or kernel of zero width may be a null pointer.
+ * Output: d_loss2[0] the data term, d_loss2[1] the regulariser term; d_G_kernel / d_G_bias STORED whole; the rows of the
+ * four tables' gradients that the batch touches STORED (duplicates of a row summed in slot order), other rows left as
+ * they are; d_flag_* (optional, uint8 per row): set to 1 for the touched rows.
+ * Work buffers: d_keys uint64 [2 batch]; d_ws float [nrhip_neumf_workspace_floats].
+ * Limits: embedding_size 0..NRHIP_NEUMF_MAX_WIDTH, 1..NRHIP_NEUMF_MAX_LAYERS layers of width 1..NRHIP_NEUMF_MAX_WIDTH,
+ * batch 0..NRHIP_NEUMF_MAX_BATCH, n_users + n_items < 2^31; outside: NRHIP_ERR_UNSUPPORTED.  batch == 0 launches nothing
+ * and writes nothing.  fp32 throughout (the reported sums are added in double and rounded once), every sum in a fixed
+ * order, no atomics: two calls on the same inputs are bit-identical. */
+#define NRHIP_NEUMF_MAX_WIDTH 128
+#define NRHIP_NEUMF_MAX_LAYERS 4
+#define NRHIP_NEUMF_MAX_BATCH 4096
+typedef struct nrhip_neumf_weights {
+  const float* d_mf_user;
+  const float* d_mf_item;
+  const float* d_mlp_user;
+  const float* d_mlp_item;
+  const float* d_kernel[NRHIP_NEUMF_MAX_LAYERS];
+  const float* d_bias[NRHIP_NEUMF_MAX_LAYERS];
+  int n_users, n_items, d, n_layers;
+  int width[NRHIP_NEUMF_MAX_LAYERS];
+} nrhip_neumf_weights;
+typedef struct nrhip_neumf_step_args {
+  nrhip_neumf_weights w;
+  float* d_G_mf_user;
+  float* d_G_mf_item;
+  float* d_G_mlp_user;
+  float* d_G_mlp_item;
+  float* d_G_kernel[NRHIP_NEUMF_MAX_LAYERS];
+  float* d_G_bias[NRHIP_NEUMF_MAX_LAYERS];
+  uint8_t* d_flag_mf_user;
+  uint8_t* d_flag_mf_item;
+  uint8_t* d_flag_mlp_user;
+  uint8_t* d_flag_mlp_item;
+  const int32_t* d_users;
+  const int32_t* d_items;
+  const float* d_labels;
+  uint64_t* d_keys;
+  float* d_ws;
+  float* d_loss2;
+  int batch, loss_kind;
+  float reg_mf, reg_mlp;
+} nrhip_neumf_step_args;
+/* Replaces the storage TensorFlow gives the intermediate tensors of the graph and their gradients: the size in floats
+ * of nrhip_neumf_step's d_ws for batches up to max_batch (only the shape fields of `weights` are read). */
+int nrhip_neumf_workspace_floats(const nrhip_neumf_weights* weights, int max_batch, size_t* floats);
+/* Replaces one `sess.run((self.loss, self.optimizer), feed_dict)` of NeuMF.py:146 up to the optimiser; the head of this
+ * section has the graph, the outputs and the limits. */
+int nrhip_neumf_step(const nrhip_neumf_step_args* args, void* stream);
+/* Replaces `sess.run(self.output, feed_dict)` of NeuMF.py:163 (candidate mode): d_out[k] = y(d_users[k], d_items[k])
+ * for n pairs, through the step's own forward path; a pair with an id outside its table scores relu-of-biases alone. */
+int nrhip_neumf_forward(const nrhip_neumf_weights* weights, const int32_t* d_users, const int32_t* d_items, int n,
+                        float* d_out, void* stream);
+/* The size in floats of nrhip_neumf_scores' d_ws for n users (only the shape fields of `weights` are read). */
+int nrhip_neumf_scores_workspace_floats(const nrhip_neumf_weights* weights, int n, size_t* floats);
+/* Replaces the per-user `sess.run(self.output, ...)` loop of NeuMF.py:165-168: d_out[r][i] = y(d_users[r], i) for every
+ * item i < n_items (row stride ld >= n_items; nothing is written beyond column n_items or row n).  The first layer is
+ * split, relu((m | n) W1 + b1) = relu((m W1u + b1) + n W1i), and made once per call for the n users and the I items; the
+ * further layers run per pair on v_mfma_f32_32x32x2_f32 (exact fp32), relu, the row sum and the GMF dot product in the
+ * epilogue; each score is written once.  At most 65535 tiles of users per call (NRHIP_ERR_UNSUPPORTED beyond). */
+int nrhip_neumf_scores(const nrhip_neumf_weights* weights, const int32_t* d_users, int n, float* d_ws, float* d_out,
+                       int64_t ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -317,6 +317,26 @@ class SrgnnStepArgs(C.Structure):
         [(n, C.c_void_p) for n in ("keys", "ws", "loss2")] + [("batch", C.c_int), ("l2", C.c_float)]
 
 
+NEUMF_MAX_LAYERS = 4
+
+
+class NeumfWeights(C.Structure):
+    """nrhip_neumf_weights (include/neurec_hip.h)"""
+    _fields_ = [(n, C.c_void_p) for n in ("mf_user", "mf_item", "mlp_user", "mlp_item")] + \
+        [("kernel", C.c_void_p * NEUMF_MAX_LAYERS), ("bias", C.c_void_p * NEUMF_MAX_LAYERS)] + \
+        [(n, C.c_int) for n in ("n_users", "n_items", "d", "n_layers")] + [("width", C.c_int * NEUMF_MAX_LAYERS)]
+
+
+class NeumfStepArgs(C.Structure):
+    """nrhip_neumf_step_args (include/neurec_hip.h)"""
+    _fields_ = [("w", NeumfWeights)] + \
+        [(n, C.c_void_p) for n in ("G_mf_user", "G_mf_item", "G_mlp_user", "G_mlp_item")] + \
+        [("G_kernel", C.c_void_p * NEUMF_MAX_LAYERS), ("G_bias", C.c_void_p * NEUMF_MAX_LAYERS)] + \
+        [(n, C.c_void_p) for n in ("flag_mf_user", "flag_mf_item", "flag_mlp_user", "flag_mlp_item", "users", "items",
+                                   "labels", "keys", "ws", "loss2")] + \
+        [("batch", C.c_int), ("loss_kind", C.c_int), ("reg_mf", C.c_float), ("reg_mlp", C.c_float)]
+
+
 # name -> argtypes; every function returns int status except where noted.
 SIGNATURES = {
     "nrhip_device_info": [C.POINTER(i32), C.POINTER(i32), psz, C.c_char_p, i32],
@@ -539,6 +559,11 @@ SIGNATURES = {
     "nrhip_srgnn_workspace_floats": [i32, i32, i32, i32, i32, psz],
     "nrhip_srgnn_step": [C.POINTER(SrgnnStepArgs), p],
     "nrhip_srgnn_forward": [C.POINTER(SrgnnWeights), C.POINTER(SrgnnFeed), i32, p, p, i64, p],
+    "nrhip_neumf_workspace_floats": [C.POINTER(NeumfWeights), i32, psz],
+    "nrhip_neumf_step": [C.POINTER(NeumfStepArgs), p],
+    "nrhip_neumf_forward": [C.POINTER(NeumfWeights), p, p, i32, p, p],
+    "nrhip_neumf_scores_workspace_floats": [C.POINTER(NeumfWeights), i32, psz],
+    "nrhip_neumf_scores": [C.POINTER(NeumfWeights), p, i32, p, p, i64, p],
 }
 
 for _name, _args in SIGNATURES.items():

@@ -64,6 +64,14 @@ MODELS = {
               ("nh", "16"), ("dropout", "0.5"), ("neg_samples", "3"), ("batch_size", "256"), ("epochs", "1000")],
     "SRGNN": [("lr", "0.001"), ("L2", "1e-5"), ("hidden_size", "64"), ("batch_size", "100"), ("epochs", "500"),
               ("lr_dc", "0.1"), ("lr_dc_step", "3"), ("step", "1"), ("nonhybrid", "False"), ("max_seq_len", "200")],
+    "NeuMF": [("epochs", "100"), ("batch_size", "256"), ("embedding_size", "16"), ("layers", "[64,32,16]"),
+              ("reg_mf", "0"), ("reg_mlp", "0"), ("is_pairwise", "False"), ("num_neg", "4"),
+              ("loss_function", "cross_entropy"), ("learning_rate", "0.001"), ("learner", "adam"),
+              ("init_method", "normal"), ("stddev", "0.01"), ("verbose", "1"), ("mf_pretrain", "pretrain/GMF"),
+              ("mlp_pretrain", "pretrain/MLP")],
+    "MLP": [("epochs", "100"), ("batch_size", "256"), ("layers", "[64,32,16]"), ("reg_mlp", "0.0"),
+            ("learning_rate", "0.001"), ("learner", "adam"), ("is_pairwise", "True"), ("num_neg", "4"),
+            ("loss_function", "bpr"), ("verbose", "1"), ("init_method", "normal"), ("stddev", "0.01")],
 }
 
 
