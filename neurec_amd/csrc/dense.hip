@@ -13,7 +13,7 @@
 // that a layer is one forward kernel and (backward) one row kernel + one weight-gradient kernel.
 //
 // Weight gradients dW = Xᵀ·G (X, G: [N][16]) are tall-skinny products reduced over the N rows:
-// they run on the fp32 matrix cores (v_mfma_f32_16x16x4_f32, one wave per 256-row slab) and are
+// they run on the fp32 matrix cores (v_mfma_f32_16x16x4_f32, one wave per 64-row slab) and are
 // combined over slabs in slab order (deterministic).
 #include "nr_common.h"
 #include <stdlib.h>
@@ -303,7 +303,7 @@ int nrhip_ngcf_layer_bwd(const float* d_ego, const float* d_S, const float* d_Wg
                          void* d_ws, size_t ws_bytes, void* stream) {
   NR_REQUIRE(d_ego && d_S && d_Wg && d_bg && d_Wb && d_bb && d_mask && d_dout && d_dS &&
                  d_dego_direct && d_dT1 && d_dT2 && d_dWg && d_dbg && d_dWb && d_dbb && d_ws &&
-                 n_rows >= 0 && ldo >= d,
+                 n_rows >= 0 && ldo >= d && keep > 0.f && keep <= 1.f,
              NR_ERR_ARG, "ngcf_layer_bwd: bad arguments");
   NR_REQUIRE(d == 16, NR_ERR_UNSUPPORTED, "ngcf_layer: layer width %d not built (16)", d);
   NR_REQUIRE(ldo % 4 == 0 && ((uintptr_t)d_dout % 16) == 0, NR_ERR_ARG,
