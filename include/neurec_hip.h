@@ -2275,6 +2275,108 @@ int nrhip_neumf_scores_workspace_floats(const nrhip_neumf_weights* weights, int 
 int nrhip_neumf_scores(const nrhip_neumf_weights* weights, const int32_t* d_users, int n, float* d_ws, float* d_out,
                        int64_t ld, void* stream);
 
+/* ---- CDAE (collaborative denoising auto-encoder, Wu et al., WSDM 2016) ------------------------------
+ * Replaces: the per-user batch loops of CDAE.train_model (model/general_recommender/CDAE.py:108-140), the graph of
+ * CDAE._encoding / build_graph (CDAE.py:62-98) up to the optimiser, and the encoder half of predict() (CDAE.py:148-160).
+ * A batch is `batch` slots, each a user u with the train row R_u.  Per slot the builder draws |R_u| num_neg items
+ * outside R_u with replacement and keeps each once, ascending: N_s.  The slot's DECODER entries are R_u ascending
+ * (label 1), then N_s (label 0); its INPUT entries are R_u and N_s merged, ascending, every value 1 (CDAE.py:118 writes the
+ * negatives into the input row).  With keep_e = the corruption mask of input entry e and k = keep_prob:
+ *     hidden_s = act(sum_e keep_e (1 / k) en[item_e]  +  user[u]  +  offset)       act: 0 identity, 1 sigmoid
+ *     x_e      = <hidden_slot(e), de[item_e]> + bias[item_e]                       over the decoder entries
+ *     loss     = sum_e pointwise_loss(kind, label_e, x_e)        kind 0: sigmoid cross-entropy, 1: square; a SUM
+ *              + reg l2_loss(en[i], de[i], bias[i] for every item i of the batch ONCE (tf.unique, CDAE.py:83);
+ *                            user[u] per slot; all of offset)
+ *
+ * nrhip_cdae_batch: draw (seed, user, q) is the q-th number of the sampler's counter-based stream (nrhip_sample_*):
+ * independent of the batch around it.  The host passes what it knows from the CSR: d_pos_ptr [batch + 1], the prefix
+ * sums of the slots' |R_u|, d_seg_off [batch + 1] = num_neg d_pos_ptr and d_seg_len [batch] = num_neg |R_u|.  The draws
+ * are sorted per slot in LDS (nrhip_sort_u64_segments) while max_draws <= NRHIP_CDAE_SEGMENT_DRAWS, by one sort of
+ * all (slot, item) keys (nrhip_sort_u64) beyond.  Output, all on the device: d_entry_ptr [batch + 1]; per entry
+ * d_items, d_labels, d_slot and d_in_pos (the index in d_in_items of the entry's own item); d_in_items (the input
+ * list; slot s holds the same range d_entry_ptr[s] .. d_entry_ptr[s + 1] in both lists).  The arrays hold
+ * (1 + num_neg) d_pos_ptr[batch] entries at most.  d_keys: scratch, num_neg d_pos_ptr[batch] keys.  Users must be rows
+ * of the CSR.  batch 0..NRHIP_CDAE_MAX_BATCH.
+ *
+ * nrhip_cdae_step: d_loss2 = (loss term, regulariser term); d_G_user / d_G_en / d_G_de / d_G_bias: the rows of the
+ * batch are STORED (keep the others zero), d_G_offset whole.  A row's gradient is the sum over its run of the sorted
+ * keys (row << 32 | entry, or slot), in key order, plus reg row once per item, once per occurrence per user.
+ * d_keep uint8 per input entry: read (keep_given) or drawn from (seed, step, entry index) and written.  d_flag_*: as in
+ * nrhip_fpmc_step.  Work buffers: d_keys uint64 and d_l2 float [entry_cap + batch], d_g float [entry_cap], d_hidden /
+ * d_dz float [batch][d], d_scal float [4 batch].  entry_cap >= d_entry_ptr[batch], which stays on the device.
+ * n_users + n_items < 2^31 - 1; d = 1..NRHIP_CDAE_MAX_D.  fp32, fixed summation orders, no atomics: bit-identical. */
+#define NRHIP_CDAE_MAX_D 128
+#define NRHIP_CDAE_MAX_BATCH 1024
+#define NRHIP_CDAE_SEGMENT_DRAWS 16384 /* draws of one slot that nrhip_sort_u64_segments sorts in LDS */
+typedef struct nrhip_cdae_batch_args {
+  const int64_t* d_indptr;
+  const int32_t* d_indices;
+  const int32_t* d_users;
+  const int64_t* d_pos_ptr;
+  const int64_t* d_seg_off;
+  const int32_t* d_seg_len;
+  uint64_t* d_keys;
+  int64_t* d_entry_ptr;
+  int32_t* d_items;
+  float* d_labels;
+  int32_t* d_slot;
+  int32_t* d_in_items;
+  int32_t* d_in_pos;
+  int64_t n_draws;
+  uint64_t seed;
+  int n_users, n_items, batch, num_neg, max_draws;
+} nrhip_cdae_batch_args;
+int nrhip_cdae_batch(const nrhip_cdae_batch_args* args, void* stream);
+typedef struct nrhip_cdae_step_args {
+  const float* d_user;
+  const float* d_en;
+  const float* d_offset;
+  const float* d_de;
+  const float* d_bias;
+  float* d_G_user;
+  float* d_G_en;
+  float* d_G_offset;
+  float* d_G_de;
+  float* d_G_bias;
+  uint8_t* d_flag_user;
+  uint8_t* d_flag_en;
+  uint8_t* d_flag_de;
+  uint8_t* d_flag_bias;
+  const int32_t* d_users;
+  const int64_t* d_entry_ptr;
+  const int32_t* d_items;
+  const float* d_labels;
+  const int32_t* d_slot;
+  const int32_t* d_in_items;
+  const int32_t* d_in_pos;
+  uint8_t* d_keep;
+  uint64_t* d_keys;
+  float* d_g;
+  float* d_hidden;
+  float* d_dz;
+  float* d_scal;
+  float* d_l2;
+  float* d_loss2;
+  uint64_t seed, step;
+  int n_users, n_items, d, batch, entry_cap, act, loss_kind, keep_given;
+  float keep_prob, reg;
+} nrhip_cdae_step_args;
+int nrhip_cdae_step(const nrhip_cdae_step_args* args, void* stream);
+/* The evaluation's user factors: d_out [batch][ld] (ld >= d + 1), row b = [hidden | 1] of u = d_users[b] (NULL: u = b)
+ * from the train row alone, so that its inner product with [de[i] | bias[i]] is predict()'s score.  The mask of the
+ * k-th entry of row b is d_keep_io[d_mask_ptr[b] + k] (d_mask_ptr: the prefix sums of the row lengths, batch + 1),
+ * read or drawn as in nrhip_cdae_step; keep_prob >= 1 keeps everything and takes NULL for both.  A user outside
+ * [0, n_users) gets [0 | 1]. */
+int nrhip_cdae_user_factors(const int64_t* d_indptr, const int32_t* d_indices, int n_users, int n_items,
+                            const float* d_user, const float* d_en, const float* d_offset, int d, int act,
+                            const int32_t* d_users, const int64_t* d_mask_ptr, int batch, uint8_t* d_keep_io,
+                            int keep_given, float keep_prob, uint64_t seed, uint64_t step, float* d_out, int64_t ld,
+                            void* stream);
+/* Candidate mode: d_out[k] = <d_factors[d_rows[k]][0..d), de[d_items[k]]> + bias[d_items[k]] for n pairs; an item
+ * outside [0, n_items) scores 0. */
+int nrhip_cdae_pairs(const float* d_factors, int64_t ld, const float* d_de, const float* d_bias, int n_items, int d,
+                     const int32_t* d_rows, const int32_t* d_items, int64_t n, float* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

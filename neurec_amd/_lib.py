@@ -337,6 +337,24 @@ class NeumfStepArgs(C.Structure):
         [("batch", C.c_int), ("loss_kind", C.c_int), ("reg_mf", C.c_float), ("reg_mlp", C.c_float)]
 
 
+class CdaeBatchArgs(C.Structure):
+    """nrhip_cdae_batch_args (include/neurec_hip.h)"""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "indptr", "indices", "users", "pos_ptr", "seg_off", "seg_len", "keys", "entry_ptr", "items", "labels", "slot",
+        "in_items", "in_pos")] + [("n_draws", C.c_int64), ("seed", C.c_uint64)] + \
+        [(n, C.c_int) for n in ("n_users", "n_items", "batch", "num_neg", "max_draws")]
+
+
+class CdaeStepArgs(C.Structure):
+    """nrhip_cdae_step_args (include/neurec_hip.h)"""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "user", "en", "offset", "de", "bias", "G_user", "G_en", "G_offset", "G_de", "G_bias", "flag_user", "flag_en",
+        "flag_de", "flag_bias", "users", "entry_ptr", "items", "labels", "slot", "in_items", "in_pos", "keep", "keys",
+        "g", "hidden", "dz", "scal", "l2", "loss2")] + [("seed", C.c_uint64), ("step", C.c_uint64)] + \
+        [(n, C.c_int) for n in ("n_users", "n_items", "d", "batch", "entry_cap", "act", "loss_kind", "keep_given")] + \
+        [("keep_prob", C.c_float), ("reg", C.c_float)]
+
+
 # name -> argtypes; every function returns int status except where noted.
 SIGNATURES = {
     "nrhip_device_info": [C.POINTER(i32), C.POINTER(i32), psz, C.c_char_p, i32],
@@ -564,6 +582,10 @@ SIGNATURES = {
     "nrhip_neumf_forward": [C.POINTER(NeumfWeights), p, p, i32, p, p],
     "nrhip_neumf_scores_workspace_floats": [C.POINTER(NeumfWeights), i32, psz],
     "nrhip_neumf_scores": [C.POINTER(NeumfWeights), p, i32, p, p, i64, p],
+    "nrhip_cdae_batch": [C.POINTER(CdaeBatchArgs), p],
+    "nrhip_cdae_step": [C.POINTER(CdaeStepArgs), p],
+    "nrhip_cdae_user_factors": [p, p, i32, i32, p, p, p, i32, i32, p, p, i32, p, i32, f32, u64, u64, p, i64, p],
+    "nrhip_cdae_pairs": [p, i64, p, p, i32, i32, p, p, i64, p, p],
 }
 
 for _name, _args in SIGNATURES.items():

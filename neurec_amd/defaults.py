@@ -72,6 +72,9 @@ MODELS = {
     "MLP": [("epochs", "100"), ("batch_size", "256"), ("layers", "[64,32,16]"), ("reg_mlp", "0.0"),
             ("learning_rate", "0.001"), ("learner", "adam"), ("is_pairwise", "True"), ("num_neg", "4"),
             ("loss_function", "bpr"), ("verbose", "1"), ("init_method", "normal"), ("stddev", "0.01")],
+    "CDAE": [("lr", "0.001"), ("reg", "0.001"), ("hidden_dim", "64"), ("dropout", "0.5"), ("num_neg", "5"),
+             ("epochs", "5000"), ("batch_size", "32"), ("hidden_act", "sigmoid"),
+             ("loss_func", "sigmoid_cross_entropy")],
 }
 
 
