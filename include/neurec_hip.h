@@ -2377,6 +2377,71 @@ int nrhip_cdae_user_factors(const int64_t* d_indptr, const int32_t* d_indices, i
 int nrhip_cdae_pairs(const float* d_factors, int64_t ld, const float* d_de, const float* d_bias, int n_items, int d,
                      const int32_t* d_rows, const int32_t* d_items, int64_t n, float* d_out, void* stream);
 
+/* ---- DeepICF (deep item-based collaborative filtering) -------------------------
+ * Replaces: the graph of model/general_recommender/DeepICF.py:112-178 and one `sess.run((loss, optimizer))` per step,
+ * and predict() (DeepICF.py:231-259).  NAIS's attention pooling (nrhip_nais_step: the same instances, mask, ragged
+ * buffer and walks) gives p; then a tower over x0 = (n^alpha p) (.) Q[i]:
+ *     per layer k  z = x W_k + b_k,  [batch norm],  relu;   out = x_L . w_out + b_out;   output = sigmoid(out + bias[i])
+ *     loss = MEAN(-y log(output + 1e-7) - (1 - y) log(1 - output + 1e-7))                        (tf.losses.log_loss)
+ *          + regs[0] l2(Q) + regs[1] l2(c1) + regs[2] l2(W) + sum_k regw[k] l2(W_k)   — WHOLE tables, so d_G_Q and d_G_c1
+ *            are dense gradients (reg * table + the batch's rows); the call zeroes d_G_Q itself
+ * Batch norm (batch_norm != 0) is the fused form of TF-1.12 on a rank-2 input, decay 0.9, epsilon 0.001: training
+ * normalises with the batch mean and the BIASED batch variance; d_mm / d_mv move by v -= (v - batch) * 0.1, the variance
+ * entering with Bessel's correction batch / max(batch - 1, 1) when bessel != 0.  The batch statistics are crossed at
+ * kernel boundaries: per-tile partial sums combined in tile order, the mean first, then the centred squares; backward
+ * likewise for sum dy and sum dy xhat.  With batch norm on, d_G_b[k] is written as exact zeros (it is zero in exact
+ * arithmetic).  An instance outside the matrix takes part in the batch statistics as a zero row (and in the mean's
+ * 1 / batch); it has no loss term and its d loss / d logit is zero, so it reaches no gradient but through those statistics.
+ * `nais`: as for nrhip_nais_step with pairwise = 0, c1_sort = 0, reg_p = reg_q = 0; loss_kind is not
+ * read.  d_ws: nrhip_deepicf_workspace_floats(tower, d, max_batch) floats.  Up to NRHIP_DEEPICF_MAX_LAYERS layers of up
+ * to NRHIP_DEEPICF_MAX_WIDTH (beyond: NRHIP_ERR_UNSUPPORTED).  Every sum is taken in a fixed order, no atomics. */
+#define NRHIP_DEEPICF_MAX_LAYERS 4
+#define NRHIP_DEEPICF_MAX_WIDTH 128
+typedef struct nrhip_deepicf_tower {
+  const float* d_W[NRHIP_DEEPICF_MAX_LAYERS];      /* [in][width] */
+  const float* d_b[NRHIP_DEEPICF_MAX_LAYERS];
+  const float* d_gamma[NRHIP_DEEPICF_MAX_LAYERS];  /* batch_norm != 0 */
+  const float* d_beta[NRHIP_DEEPICF_MAX_LAYERS];
+  float* d_mm[NRHIP_DEEPICF_MAX_LAYERS];           /* moving mean / variance */
+  float* d_mv[NRHIP_DEEPICF_MAX_LAYERS];
+  const float* d_Wout;                             /* [width of the last layer] */
+  const float* d_bout;                             /* [1] */
+  int n_layers, batch_norm;
+  int width[NRHIP_DEEPICF_MAX_LAYERS];
+} nrhip_deepicf_tower;
+typedef struct nrhip_deepicf_step_args {
+  nrhip_nais_step_args nais;
+  nrhip_deepicf_tower tower;
+  float* d_G_W[NRHIP_DEEPICF_MAX_LAYERS];
+  float* d_G_b[NRHIP_DEEPICF_MAX_LAYERS];
+  float* d_G_gamma[NRHIP_DEEPICF_MAX_LAYERS];
+  float* d_G_beta[NRHIP_DEEPICF_MAX_LAYERS];
+  float* d_G_Wout;
+  float* d_G_bout;
+  float* d_ws;
+  float regs[3];
+  float regw[NRHIP_DEEPICF_MAX_LAYERS];            /* 0: the layer is not regularised */
+  int bessel;
+} nrhip_deepicf_step_args;
+int nrhip_deepicf_workspace_floats(const nrhip_deepicf_tower* tower, int d, int max_batch, size_t* floats);
+int nrhip_deepicf_step(const nrhip_deepicf_step_args* args, void* stream);
+/* predict(): d_out [batch][ld], row b = sigmoid(tower(|R_u|^alpha v(u, i) (.) Q[i]) + bias[i]) for every item i, with
+ * v(u, i) = sum_{h in R_u} e(i, h) c1[h] / (sum_{h in R_u} e(i, h))^beta pooled per (user, item) in registers — no
+ * [batch][items][d] block exists.  `nais`: as for nrhip_nais_scores (its workspace, tile, h_cap and mfma); the e(i, h)
+ * terms are nais.hip's.  d_wpad: the tower at inference as ONE affine map per layer (the caller folds the moving
+ * statistics in): per layer the kernel [32 Kt][32 Mt] zero-padded then the bias [32 Mt], then w_out [32 Mt] and b_out;
+ * tiles[k] = 32-tiles of the width in front of layer k (tiles[0]: of d) .. tiles[n_layers]: of the last width.
+ * mfma != 0: the tower on v_mfma_f32_32x32x2_f32, a wavefront per (user, 32 items), widths up to 64 (beyond:
+ * NRHIP_ERR_UNSUPPORTED); mfma == 0: one lane per pair, any width up to NRHIP_DEEPICF_MAX_WIDTH.  A user without train
+ * items (or outside the matrix) scores through an empty pooling (v = 0).  Reads every table, writes d_out alone. */
+typedef struct nrhip_deepicf_scores_args {
+  nrhip_nais_scores_args nais;
+  const float* d_wpad;
+  int n_layers, mfma, wtotal;
+  int tiles[NRHIP_DEEPICF_MAX_LAYERS + 1];
+} nrhip_deepicf_scores_args;
+int nrhip_deepicf_scores(const nrhip_deepicf_scores_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -355,6 +355,30 @@ class CdaeStepArgs(C.Structure):
         [("keep_prob", C.c_float), ("reg", C.c_float)]
 
 
+DEEPICF_MAX_LAYERS = 4
+
+
+class DeepicfTower(C.Structure):
+    """nrhip_deepicf_tower (include/neurec_hip.h)"""
+    _fields_ = [(n, C.c_void_p * DEEPICF_MAX_LAYERS) for n in ("W", "b", "gamma", "beta", "mm", "mv")] + \
+        [("Wout", C.c_void_p), ("bout", C.c_void_p), ("n_layers", C.c_int), ("batch_norm", C.c_int),
+         ("width", C.c_int * DEEPICF_MAX_LAYERS)]
+
+
+class DeepicfStepArgs(C.Structure):
+    """nrhip_deepicf_step_args (include/neurec_hip.h)"""
+    _fields_ = [("nais", NaisStepArgs), ("tower", DeepicfTower)] + \
+        [(n, C.c_void_p * DEEPICF_MAX_LAYERS) for n in ("G_W", "G_b", "G_gamma", "G_beta")] + \
+        [("G_Wout", C.c_void_p), ("G_bout", C.c_void_p), ("ws", C.c_void_p), ("regs", C.c_float * 3),
+         ("regw", C.c_float * DEEPICF_MAX_LAYERS), ("bessel", C.c_int)]
+
+
+class DeepicfScoresArgs(C.Structure):
+    """nrhip_deepicf_scores_args (include/neurec_hip.h)"""
+    _fields_ = [("nais", NaisScoresArgs), ("wpad", C.c_void_p), ("n_layers", C.c_int), ("mfma", C.c_int),
+                ("wtotal", C.c_int), ("tiles", C.c_int * (DEEPICF_MAX_LAYERS + 1))]
+
+
 # name -> argtypes; every function returns int status except where noted.
 SIGNATURES = {
     "nrhip_device_info": [C.POINTER(i32), C.POINTER(i32), psz, C.c_char_p, i32],
@@ -586,6 +610,9 @@ SIGNATURES = {
     "nrhip_cdae_step": [C.POINTER(CdaeStepArgs), p],
     "nrhip_cdae_user_factors": [p, p, i32, i32, p, p, p, i32, i32, p, p, i32, p, i32, f32, u64, u64, p, i64, p],
     "nrhip_cdae_pairs": [p, i64, p, p, i32, i32, p, p, i64, p, p],
+    "nrhip_deepicf_workspace_floats": [C.POINTER(DeepicfTower), i32, i32, psz],
+    "nrhip_deepicf_step": [C.POINTER(DeepicfStepArgs), p],
+    "nrhip_deepicf_scores": [C.POINTER(DeepicfScoresArgs), p],
 }
 
 for _name, _args in SIGNATURES.items():

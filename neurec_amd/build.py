@@ -22,7 +22,7 @@ SOURCES = ["eval_select.hip", "score_gemm.hip", "sampler.hip", "spmm.hip", "bpr.
            "step.hip", "dense.hip", "vae.hip", "spmm_blocked.hip", "route.hip", "gemm.hip", "vae_wide.hip", "ngcf_wide.hip", "vae_fused.hip",
            "score_bf16.hip", "score_i8.hip", "eval_pipeline.hip", "wrmf.hip", "itemknn.hip", "fism.hip", "nais.hip", "fpmc.hip", "fossil.hip", "hrm.hip",
            "npe.hip", "fpmcplus.hip", "transrec.hip", "gru4rec.hip", "gru4recplus.hip", "sasrec.hip", "caser.hip", "srgnn.hip",
-           "neumf.hip", "cdae.hip"]
+           "neumf.hip", "cdae.hip", "deepicf.hip"]
 # per-file flags.  score_i8.hip: MFMA results in the unified VGPR file instead of AGPRs — its epilogue reads every
 # accumulator of two sets per tile, and v_accvgpr_read per element doubled its VALU work (896 -> 78 reads in the loop)
 FILE_FLAGS = {"score_i8.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
@@ -30,7 +30,7 @@ FILE_FLAGS = {"score_i8.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 # nothing of it is linked into the product
 EXP_SOURCES = ["experiments/gather_experiments.hip"]
 EXP_LIB_PATH = os.path.join(HERE, "libneurec_exp.so")
-HEADERS = ["nr_core.h", "nr_common.h", "rowkey_common.h", "history_common.h", "spmm_blocked_plan.h",
+HEADERS = ["nr_core.h", "nr_common.h", "rowkey_common.h", "history_common.h", "nais_kernels.h", "spmm_blocked_plan.h",
            "spmm_blocked_factor.h", "spmm_wanted_plan.h", "gru4rec_cell.h"]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

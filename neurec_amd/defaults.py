@@ -75,6 +75,12 @@ MODELS = {
     "CDAE": [("lr", "0.001"), ("reg", "0.001"), ("hidden_dim", "64"), ("dropout", "0.5"), ("num_neg", "5"),
              ("epochs", "5000"), ("batch_size", "32"), ("hidden_act", "sigmoid"),
              ("loss_func", "sigmoid_cross_entropy")],
+    "DeepICF": [("pretrain_file", "None"), ("verbose", "1"), ("learner", "adam"), ("batch_size", "256"),
+                ("epochs", "300"), ("layers", "[64,32,16]"), ("weight_size", "16"), ("embedding_size", "16"),
+                ("data_alpha", "0"), ("regs", "[0.000001,0.000001,0.00001]"), ("regw", "[10,10]"), ("alpha", "0"),
+                ("beta", "0.5"), ("num_neg", "4"), ("learning_rate", "0.001"), ("activation", "Relu"),
+                ("algorithm", "1"), ("batch_norm", "1"), ("embed_init_method", "tnormal"),
+                ("weight_init_method", "he_normal"), ("bias_init_method", "he_normal"), ("stddev", "0.01")],
 }
 
 

@@ -6,6 +6,8 @@ item or none, count).  Both engines hold c1 / Q / bias, the train matrix and its
 table, the instance buffers of a batch, and run one C call per step followed by the same applications: `c1` and the
 model's dense variables through the dense Apply* kernels (or c1 by rows, `c1_application="rows"`), `embedding_Q` and
 `bias` by rows — the forms TF-1.12 picks for tf.concat reads and embedding_lookup reads (neurec_amd/row_learner.py).
+`q_application="dense"` gives `embedding_Q` the dense application: the form of a model whose loss also reads the whole
+table (DeepICF's regulariser), whose step then leaves a dense gradient in G["Q"].
 """
 import ctypes as C
 
@@ -25,12 +27,14 @@ class HistoryEngine:
     NAME, MAX_D, ARGS, STEP = None, 128, None, None
 
     def __init__(self, c1, Q, train, lr, regs, alpha, max_batch, loss, pairwise, learner, bias, momentum,
-                 c1_application, dense=None, sorted_rows=False):
+                 c1_application, dense=None, sorted_rows=False, q_application="rows"):
         """dense(d): the model's further variables {name: float32 tensor}, checked against embedding_size d — dense
         variables to TF; sorted_rows: de-duplicate the train rows and sort their columns"""
         loss, learner, self.loss_kind = check_loss_learner(loss, learner, pairwise)
         if c1_application not in ("dense", "rows"):
             raise ValueError("c1_application is 'dense' or 'rows', got %r" % (c1_application,))
+        if q_application not in ("dense", "rows"):
+            raise ValueError("q_application is 'dense' or 'rows', got %r" % (q_application,))
         c1, Q = f32(c1), f32(Q)
         if c1.dim() != 2 or tuple(c1.shape) != tuple(Q.shape):
             raise ValueError("c1 and embedding_Q must both be [num_items, embedding_size]")
@@ -56,6 +60,7 @@ class HistoryEngine:
             setattr(self, k, t.contiguous().to(dev))
         self._dense_names = tuple(more)
         self._names = ("c1", "Q", "bias") + self._dense_names
+        self._shared_names = self._names                       # the tables the shared part of the struct names
         self.G = {k: torch.zeros_like(getattr(self, k)) for k in self._names}
         self.lr, self.momentum, self.alpha = float(lr), float(momentum), float(alpha)
         self.reg_p, self.reg_q = float(regs[0]), float(regs[1])
@@ -64,7 +69,8 @@ class HistoryEngine:
         self.dense = self.opt.dense                           # the dense variables' learner; None: ApplyAdam
         slots = {k: self.opt.slots(getattr(self, k)) for k in self._names}
         self.s0, self.s1 = ({k: s[i] for k, s in slots.items()} for i in (0, 1))
-        self.flag_Q, self.flag_bias = self.opt.flag(I, dev), self.opt.flag(I, dev)
+        self.q_dense = q_application == "dense"
+        self.flag_Q, self.flag_bias = None if self.q_dense else self.opt.flag(I, dev), self.opt.flag(I, dev)
         # 'rows': c1 gets the sparse application too, on the rows the batch's histories hold (what TF does when the
         # gradient of c1 reaches its optimizer as IndexedSlices); 'dense' (default): the Apply* kernels on every row
         self.c1_rows = c1_application == "rows"
@@ -92,6 +98,11 @@ class HistoryEngine:
         """the device address of a batch field"""
         return _ptr(t, dtype)
 
+    def _shared(self, A):
+        """the part of the argument struct that names the fields shared by the history models (the struct itself,
+        unless the model's struct nests it)"""
+        return A
+
     def _apply_more(self):
         """the applications of a model's tables beyond c1 / Q / bias and its dense variables"""
 
@@ -103,10 +114,11 @@ class HistoryEngine:
         if items.numel() != B or third.numel() != B:
             raise ValueError("users, items and the third field must have the same length")
         self.t += 1
-        a = self.ARGS()
+        A = self.ARGS()
+        a = self._shared(A)
         a.indptr, a.indices = _ptr(self.csr.indptr, torch.int64), _ptr(self.csr.indices, torch.int32)
         a.t_indptr, a.t_users = _ptr(self.csc.indptr, torch.int64), _ptr(self.csc.indices, torch.int32)
-        for k in self._names:
+        for k in self._shared_names:
             setattr(a, k, _ptr(getattr(self, k)))
             setattr(a, "G_" + k, _ptr(self.G[k]))
         a.flag_Q, a.flag_bias, a.flag_c1 = addr(self.flag_Q), addr(self.flag_bias), addr(self.flag_c1)
@@ -117,17 +129,19 @@ class HistoryEngine:
         a.n_users, a.n_items, a.d, a.batch = self.n_users, self.n_items, self.d, B
         a.pairwise, a.loss_kind, a.step = int(self.pairwise), self.loss_kind, self.t
         a.alpha, a.reg_p, a.reg_q = self.alpha, self.reg_p, self.reg_q
-        self._fill(a)
-        call(self.STEP, C.byref(a), _stream())
+        self._fill(A)
+        call(self.STEP, C.byref(A), _stream())
 
     def apply(self):
         """the applications of self.G, in the order TF-1.12 runs them here"""
+        dense = (("Q",) if self.q_dense else ()) + self._dense_names
         if self.c1_rows:
             self._apply_rows("c1", self.flag_c1)
-            self._apply_dense(self._dense_names)
+            self._apply_dense(dense)
         else:
-            self._apply_dense(("c1",) + self._dense_names)
-        self._apply_rows("Q", self.flag_Q)
+            self._apply_dense(("c1",) + dense)
+        if not self.q_dense:
+            self._apply_rows("Q", self.flag_Q)
         self._apply_rows("bias", self.flag_bias)
         self._apply_more()
         self.adam.advance()

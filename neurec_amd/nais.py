@@ -52,7 +52,10 @@ class NAISEngine(HistoryEngine):
 
     def __init__(self, c1, Q, W, b, train, lr, regs, alpha, beta, max_batch, algorithm=0, activation=None,
                  loss="cross_entropy", pairwise=False, learner="adam", bias=None, h=None, momentum=0.9,
-                 attention_mask="reference", c1_application="dense", c1_path=C1_PATH, pair_kernel="auto"):
+                 attention_mask="reference", c1_application="dense", c1_path=C1_PATH, pair_kernel="auto",
+                 more_dense=None, q_application="rows"):
+        """more_dense(d): further dense variables of a model that pools as NAIS does (neurec_amd/deepicf.py);
+        q_application: HistoryEngine's"""
         if attention_mask not in ("reference", "history"):
             raise ValueError("attention_mask is 'reference' or 'history', got %r" % (attention_mask,))
         if algorithm not in (0, 1):
@@ -74,10 +77,10 @@ class NAISEngine(HistoryEngine):
             ht = torch.ones(w) if h is None else f32(h).reshape(-1)
             if bt.numel() != w or ht.numel() != w:
                 raise ValueError("b and h must hold weight_size entries")
-            return {"W": Wt, "b": bt, "h": ht}
+            return dict({"W": Wt, "b": bt, "h": ht}, **(more_dense(d) if more_dense else {}))
         # sorted rows: the walk finds an item in a row by bisection.  regs[2] is read and never used (NAIS.py:33)
         HistoryEngine.__init__(self, c1, Q, train, lr, regs, alpha, max_batch, loss, pairwise, learner, bias, momentum,
-                               c1_application, dense=attention, sorted_rows=True)
+                               c1_application, dense=attention, sorted_rows=True, q_application=q_application)
         dev, d, N = self.c1.device, self.d, self._N
         w = self.w = int(self.W.shape[1])
         mfma_ok = algorithm == 0 and d <= 16 and w <= 16
@@ -168,8 +171,13 @@ class NAISEngine(HistoryEngine):
         HistoryEngine.step(self, users, items, third, loss_out)
 
     # ------------------------------------------------------------------ scoring
-    def score(self, users):
-        """S [B, I] float32 on the device: NAIS.py:246-257 for `users`, every item, own items included"""
+    def _scores_call(self, a):
+        call("nrhip_nais_scores", C.byref(a), _stream())
+
+    def score(self, users, call=None):
+        """S [B, I] float32 on the device: NAIS.py:246-257 for `users`, every item, own items included.  call(a): what
+        runs per block of users on the filled argument struct (None: nrhip_nais_scores)"""
+        call = call or self._scores_call
         dev = self.c1.device
         if isinstance(users, torch.Tensor):
             h_users = users.detach().cpu().numpy().astype(np.int64)
@@ -203,7 +211,7 @@ class NAISEngine(HistoryEngine):
             blk = users[s:s + 65535]
             a = NaisScoresArgs()
             a.indptr, a.indices = _ptr(self.csr.indptr, torch.int64), _ptr(self.csr.indices, torch.int32)
-            a.c1, a.Q, a.bias, a.W, a.b, a.h = (_ptr(getattr(self, k)) for k in self._names)
+            a.c1, a.Q, a.bias, a.W, a.b, a.h = (_ptr(getattr(self, k)) for k in self._names[:6])
             a.users, a.out = _ptr(blk, torch.int32), C.c_void_p(out[s:].data_ptr())
             a.map, a.hs, a.cnt = _ptr(self._map), _ptr(self._hs), _ptr(self._cnt)
             a.E, a.F = C.c_void_p(self._EF.data_ptr()), C.c_void_p(self._EF.data_ptr() + 4 * h_cap * tile)
@@ -214,6 +222,6 @@ class NAISEngine(HistoryEngine):
             a.algorithm, a.activation, a.batch = self.algorithm, self.activation, int(blk.numel())
             a.h_cap, a.tile, a.project, a.mfma = h_cap, tile, project, int(self.mfma)
             a.alpha, a.beta = self.alpha, self.beta
-            call("nrhip_nais_scores", C.byref(a), _stream())
+            call(a)
             project = 0
         return out
