@@ -2442,6 +2442,68 @@ typedef struct nrhip_deepicf_scores_args {
 } nrhip_deepicf_scores_args;
 int nrhip_deepicf_scores(const nrhip_deepicf_scores_args* args, void* stream);
 
+/* ---- ConvNCF: the outer-product conv tower's step, the pairs' outputs and the all-items scorer (csrc/convncf.hip).
+ * These symbols are additions: no existing struct changes and NRHIP_ABI_VERSION stays 4.
+ * nrhip_convncf_step replaces one `sess.run((self.loss, self.optimizer), feed_dict)` of ConvNCF.py:177 up to the two
+ * Adagrad applications: the graph of ConvNCF.py:87-125 on `batch` triplets (user, pos, neg) and its gradients.
+ *   E = P[u] (x) Q[i] [d, d, 1]; n_layers layers tanh(conv2d(x, kernel_k [2, 2, c_in, c_out], strides 2, SAME) + bias_k)
+ *   with d == 2^n_layers, so the last layer has one position; output = a_last . W + b (no sigmoid);
+ *   loss = sum pairwise_loss(output(u, pos) - output(u, neg))  (loss_kind: 0 bpr, 1 hinge, 2 square)
+ *   opt_loss = loss + reg_embed l2_loss(P[u], Q[neg], Q[pos]) + reg_head l2_loss(W, b)
+ *              + reg_net (sum_k l2_loss(kernel_k, bias_k) + l2_loss(W, b)),  l2_loss = sum / 2, on the GATHERED rows: the
+ *   user row counts once per triplet, each item row once per occurrence.
+ * Outputs: d_G_kernel / d_G_bias / d_G_W / d_G_b in full (stored); of d_G_P / d_G_Q the rows the batch holds (stored: a
+ * row's gradient is the sum over its occurrences in key order; other rows are left as they are); d_flag_P / d_flag_Q
+ * (uint8 per row, may be NULL): set to 1 for those rows (nrhip_optimizer_rows_tf); d_loss2 = {loss, the reg_embed term}.
+ * A triplet with an id outside its table takes no part.  Work buffers: d_keys uint64 [4 batch]; d_ws float
+ * [nrhip_convncf_workspace_floats] (the activations of layers 2.. between the passes, the slots, the chunks' partials).
+ * Limits: 1..NRHIP_CONVNCF_MAX_LAYERS layers of 1..NRHIP_CONVNCF_MAX_CHANNELS channels, d == 2^n_layers, batch
+ * 0..NRHIP_CONVNCF_MAX_BATCH, n_users + n_items < 2^31; outside: NRHIP_ERR_UNSUPPORTED.  batch == 0 launches nothing and
+ * writes nothing.  Sums run in a fixed order, no atomics: reruns are bit-identical. */
+#define NRHIP_CONVNCF_MAX_LAYERS 6
+#define NRHIP_CONVNCF_MAX_CHANNELS 32
+#define NRHIP_CONVNCF_MAX_BATCH 4096
+typedef struct nrhip_convncf_weights {
+  const float* d_P;             /* embedding_P [n_users][d] */
+  const float* d_Q;             /* embedding_Q [n_items][d] */
+  const float* d_kernel[NRHIP_CONVNCF_MAX_LAYERS];   /* [2][2][c_in][c_out], c_in = 1 for the first */
+  const float* d_bias[NRHIP_CONVNCF_MAX_LAYERS];
+  const float* d_W;             /* [channel[n_layers - 1]] */
+  const float* d_b;             /* [1] */
+  int n_users, n_items, d, n_layers;
+  int channel[NRHIP_CONVNCF_MAX_LAYERS];
+} nrhip_convncf_weights;
+typedef struct nrhip_convncf_step_args {
+  nrhip_convncf_weights w;
+  float* d_G_P;
+  float* d_G_Q;
+  float* d_G_kernel[NRHIP_CONVNCF_MAX_LAYERS];
+  float* d_G_bias[NRHIP_CONVNCF_MAX_LAYERS];
+  float* d_G_W;
+  float* d_G_b;
+  uint8_t* d_flag_P;
+  uint8_t* d_flag_Q;
+  const int32_t* d_users;
+  const int32_t* d_pos;
+  const int32_t* d_neg;
+  uint64_t* d_keys;
+  float* d_ws;
+  float* d_loss2;
+  int batch, loss_kind;
+  float reg_embed, reg_head, reg_net;
+} nrhip_convncf_step_args;
+/* The size in floats of nrhip_convncf_step's d_ws for batches up to max_batch (only the shape fields are read). */
+int nrhip_convncf_workspace_floats(const nrhip_convncf_weights* weights, int max_batch, size_t* floats);
+int nrhip_convncf_step(const nrhip_convncf_step_args* args, void* stream);
+/* d_out[k] = output(d_users[k], d_items[k]), k < n, through the step's forward path; a pair outside the tables gives 0 */
+int nrhip_convncf_pairs(const nrhip_convncf_weights* weights, const int32_t* d_users, const int32_t* d_items, int n,
+                        float* d_out, void* stream);
+/* d_out[r * ld + i] = output(d_users[r], i) for r < n and every item i: predict() of ConvNCF.py:196-199; ld >= n_items,
+ * the columns behind n_items are left as they are.  Any number of pairs: a launch holds at most 2^20 workgroups, each of
+ * which takes its pairs in turn (nrhip_convncf_pairs likewise) */
+int nrhip_convncf_scores(const nrhip_convncf_weights* weights, const int32_t* d_users, int n, float* d_out, int64_t ld,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -355,6 +355,26 @@ class CdaeStepArgs(C.Structure):
         [("keep_prob", C.c_float), ("reg", C.c_float)]
 
 
+CONVNCF_MAX_LAYERS = 6
+
+
+class ConvncfWeights(C.Structure):
+    """nrhip_convncf_weights (include/neurec_hip.h)"""
+    _fields_ = [("P", C.c_void_p), ("Q", C.c_void_p)] + \
+        [("kernel", C.c_void_p * CONVNCF_MAX_LAYERS), ("bias", C.c_void_p * CONVNCF_MAX_LAYERS)] + \
+        [("W", C.c_void_p), ("b", C.c_void_p)] + \
+        [(n, C.c_int) for n in ("n_users", "n_items", "d", "n_layers")] + [("channel", C.c_int * CONVNCF_MAX_LAYERS)]
+
+
+class ConvncfStepArgs(C.Structure):
+    """nrhip_convncf_step_args (include/neurec_hip.h)"""
+    _fields_ = [("w", ConvncfWeights), ("G_P", C.c_void_p), ("G_Q", C.c_void_p)] + \
+        [("G_kernel", C.c_void_p * CONVNCF_MAX_LAYERS), ("G_bias", C.c_void_p * CONVNCF_MAX_LAYERS)] + \
+        [(n, C.c_void_p) for n in ("G_W", "G_b", "flag_P", "flag_Q", "users", "pos", "neg", "keys", "ws", "loss2")] + \
+        [("batch", C.c_int), ("loss_kind", C.c_int), ("reg_embed", C.c_float), ("reg_head", C.c_float),
+         ("reg_net", C.c_float)]
+
+
 DEEPICF_MAX_LAYERS = 4
 
 
@@ -613,6 +633,10 @@ SIGNATURES = {
     "nrhip_deepicf_workspace_floats": [C.POINTER(DeepicfTower), i32, i32, psz],
     "nrhip_deepicf_step": [C.POINTER(DeepicfStepArgs), p],
     "nrhip_deepicf_scores": [C.POINTER(DeepicfScoresArgs), p],
+    "nrhip_convncf_workspace_floats": [C.POINTER(ConvncfWeights), i32, psz],
+    "nrhip_convncf_step": [C.POINTER(ConvncfStepArgs), p],
+    "nrhip_convncf_pairs": [C.POINTER(ConvncfWeights), p, p, i32, p, p],
+    "nrhip_convncf_scores": [C.POINTER(ConvncfWeights), p, i32, p, i64, p],
 }
 
 for _name, _args in SIGNATURES.items():

@@ -81,6 +81,10 @@ MODELS = {
                 ("beta", "0.5"), ("num_neg", "4"), ("learning_rate", "0.001"), ("activation", "Relu"),
                 ("algorithm", "1"), ("batch_norm", "1"), ("embed_init_method", "tnormal"),
                 ("weight_init_method", "he_normal"), ("bias_init_method", "he_normal"), ("stddev", "0.01")],
+    "ConvNCF": [("epochs", "100"), ("batch_size", "512"), ("embedding_size", "64"), ("regs", "[0.01,0,0]"),
+                ("net_channel", "[32,32,32,32,32,32]"), ("lr_embed", "0.05"), ("lr_net", "0.05"),
+                ("num_negatives", "4"), ("loss_function", "BPR"), ("keep", "1.0"), ("embed_init_method", "tnormal"),
+                ("weight_init_method", "xavier_normal"), ("stddev", "0.01"), ("verbose", "1")],
 }
 
 

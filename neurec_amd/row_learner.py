@@ -26,11 +26,12 @@ def check_loss_learner(loss, learner, pairwise):
     return loss, learner, table[loss]
 
 
-def slot_init(learner):
+def slot_init(learner, accumulator=1e-8):
     """(what TF creates the first slot with, None: the learner has no slot; whether there is a second slot, which starts
-    at zero) — adam: m, v; adagrad: the accumulator (learner.py:6); rmsprop: rms, its unused momentum; momentum: the
+    at zero) — adam: m, v; adagrad: the accumulator (learner.py:6 passes 1e-8; `accumulator` for a model that builds
+    its own tf.train.AdagradOptimizer, whose default is 0.1); rmsprop: rms, its unused momentum; momentum: the
     accumulator"""
-    return {"adam": 0.0, "gd": None, "adagrad": 1e-8, "rmsprop": 1.0, "momentum": 0.0}[learner], \
+    return {"adam": 0.0, "gd": None, "adagrad": accumulator, "rmsprop": 1.0, "momentum": 0.0}[learner], \
         learner in ("adam", "rmsprop")
 
 
@@ -38,9 +39,9 @@ class RowLearner:
     """One learner of learner.py for the variables of one engine: `adam_state` is the engine's E.AdamState (the engine
     advances it, once per step); `momentum` is MomentumOptimizer's, for the rows and the dense variables alike."""
 
-    def __init__(self, learner, lr, momentum, adam_state):
+    def __init__(self, learner, lr, momentum, adam_state, accumulator=1e-8):
         self.learner, self.lr, self.momentum, self.adam = learner, float(lr), float(momentum), adam_state
-        self.first, self.two = slot_init(learner)
+        self.first, self.two = slot_init(learner, accumulator)
         self.dense = None if learner == "adam" else E.DenseLearner(learner, lr, momentum)
 
     def slots(self, var):
