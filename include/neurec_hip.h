@@ -2504,6 +2504,87 @@ int nrhip_convncf_pairs(const nrhip_convncf_weights* weights, const int32_t* d_u
 int nrhip_convncf_scores(const nrhip_convncf_weights* weights, const int32_t* d_users, int n, float* d_out, int64_t ld,
                          void* stream);
 
+/* ---- CFGAN: the per-epoch masks, the two adversarial steps and the scorer's row factors (csrc/cfgan.hip).
+ * These symbols are additions: no existing struct changes and NRHIP_ABI_VERSION stays 4.
+ * R is the train matrix in CSR ([n_rows][n_cols], ascending rows; already transposed in itemBased mode); c is a row of
+ * it as a 0/1 vector.  Both networks are stacks of dense layers [in][out] with sigmoid hidden layers and an identity
+ * output layer: G maps n_cols -> width[0..n_hidden) -> n_cols, D maps 2 n_cols -> width[0..n_hidden) -> 1 on [c | y].
+ * A dense c, the [batch][2 n_cols] concatenation and a dense mask never exist: first layers pool rows of the kernel over
+ * the CSR row, masks are bit rows of words = ceil(n_cols / 32) uint32, column 32 w + k at bit k of word w.
+ *
+ * nrhip_cfgan_masks: per batch row b and plane (0: d_zr, 1: d_pm) one bit row: the row's train columns plus the
+ * d_n_sample[2 b + plane] other columns with the smallest (key, column) pairs, key = the upper word of
+ * splitmix64(base + column), base a splitmix64 chain over (seed, epoch, plane, row id): a pure function of those four,
+ * found by a radix select over 256-bin histograms in LDS, one workgroup per (row, plane); no key is ever stored.
+ * A count outside [0, n_cols - deg] is clamped.
+ *
+ * nrhip_cfgan_d_step / nrhip_cfgan_g_step: the forward pass and the gradients of one sess.run(trainer_d) /
+ * sess.run(trainer_g) of CFGAN.py:60-95 WITHOUT the regularisers and the optimiser (nrhip_cfgan_apply carries both).
+ *   out = G(c), y_fake = out . pm
+ *   D: mean softplus(-D([c | c])) + mean softplus(D([c | y_fake]))  -> d_loss3[0], d_loss3[1]; dis.d_G_* stored in full
+ *   G: mean softplus(-D([c | y_fake])) + zr_coef mean sum_i out_i^2 zr_i -> d_loss3[0], d_loss3[2]; gen.d_G_* stored
+ * The row gradients of the pooled kernel halves are summed along sorted (column << 32 | slot) keys in key order; every
+ * float sum has a fixed order and nothing is accumulated with floating-point atomics: reruns are bit-identical.
+ * d_ent_ptr [batch + 1]: the running sum of the batch rows' lengths (n_ent = its last entry); d_keys uint64 [n_ent];
+ * d_ws / d_gemm_ws: nrhip_cfgan_workspace for max_batch.  batch == 0 launches nothing.
+ *
+ * nrhip_cfgan_apply: one pass over every kernel and bias of `net`: gradient = d_G + reg * variable, ApplyAdam (sgd == 0;
+ * step = alpha) or ApplyGradientDescent (sgd != 0; step = the learning rate), the gradient zero afterwards, and
+ * *d_reg_loss = reg * sum(variable^2) / 2 of the values BEFORE the update.  d_partials: NRHIP_CFGAN_APPLY_BLOCKS doubles.
+ *
+ * nrhip_cfgan_hidden: d_out [batch][ld] (ld >= width[n_hidden - 1]), row b = G's last hidden layer on row d_rows[b] of R
+ * (NULL: row b); d_tmp: 2 * batch * NRHIP_CFGAN_MAX_WIDTH floats (unused with one hidden layer).
+ * nrhip_cfgan_pairs: d_out[e] = sum_k d_F[d_rows[e]][k] * d_Q[d_items[e]][k], k < width.
+ * Limits: 1..NRHIP_CFGAN_MAX_HIDDEN hidden layers of 1..NRHIP_CFGAN_MAX_WIDTH units, batch 0..NRHIP_CFGAN_MAX_BATCH,
+ * n_cols < 2^24; outside: NRHIP_ERR_UNSUPPORTED. */
+#define NRHIP_CFGAN_MAX_HIDDEN 3
+#define NRHIP_CFGAN_MAX_WIDTH 512
+#define NRHIP_CFGAN_MAX_BATCH 1024
+#define NRHIP_CFGAN_APPLY_BLOCKS 2048
+typedef struct nrhip_cfgan_net {
+  float* d_W[NRHIP_CFGAN_MAX_HIDDEN + 1];     /* layer k's kernel [in][out]; layer n_hidden is the output layer */
+  float* d_b[NRHIP_CFGAN_MAX_HIDDEN + 1];
+  float* d_G_W[NRHIP_CFGAN_MAX_HIDDEN + 1];   /* the gradients */
+  float* d_G_b[NRHIP_CFGAN_MAX_HIDDEN + 1];
+  float* d_m_W[NRHIP_CFGAN_MAX_HIDDEN + 1];   /* Adam's moments (not read with sgd) */
+  float* d_m_b[NRHIP_CFGAN_MAX_HIDDEN + 1];
+  float* d_v_W[NRHIP_CFGAN_MAX_HIDDEN + 1];
+  float* d_v_b[NRHIP_CFGAN_MAX_HIDDEN + 1];
+  int n_hidden;
+  int width[NRHIP_CFGAN_MAX_HIDDEN];
+} nrhip_cfgan_net;
+typedef struct nrhip_cfgan_step_args {
+  nrhip_cfgan_net gen;
+  nrhip_cfgan_net dis;
+  const int64_t* d_indptr;
+  const int32_t* d_indices;
+  const int32_t* d_rows;          /* [batch] rows of R, repeats allowed */
+  const int64_t* d_ent_ptr;       /* [batch + 1] */
+  const uint32_t* d_zr;           /* [batch][words] */
+  const uint32_t* d_pm;
+  uint64_t* d_keys;
+  float* d_ws;
+  void* d_gemm_ws;
+  size_t gemm_ws_bytes;
+  float* d_loss3;
+  int n_rows, n_cols, batch, n_ent, max_batch;
+  float zr_coef;
+} nrhip_cfgan_step_args;
+/* the sizes of d_ws (floats) and d_gemm_ws (bytes) for batches up to max_batch (only the shape fields are read) */
+int nrhip_cfgan_workspace(const nrhip_cfgan_step_args* shape, size_t* floats, size_t* gemm_bytes);
+int nrhip_cfgan_masks(const int64_t* d_indptr, const int32_t* d_indices, const int32_t* d_rows,
+                      const int32_t* d_n_sample, int batch, int n_rows, int n_cols, uint64_t seed, uint64_t epoch,
+                      uint32_t* d_zr, uint32_t* d_pm, void* stream);
+int nrhip_cfgan_d_step(const nrhip_cfgan_step_args* args, void* stream);
+int nrhip_cfgan_g_step(const nrhip_cfgan_step_args* args, void* stream);
+int nrhip_cfgan_apply(const nrhip_cfgan_net* net, int n_in, int n_out, int sgd, float step, float beta1, float beta2,
+                      float eps, float reg, double* d_partials, float* d_reg_loss, void* stream);
+int nrhip_cfgan_hidden(const nrhip_cfgan_net* net, const int64_t* d_indptr, const int32_t* d_indices,
+                       const int32_t* d_rows, int batch, int n_cols, float* d_tmp, float* d_out, int64_t ld,
+                       void* stream);
+int nrhip_cfgan_pairs(const float* d_F, int64_t ldf, const float* d_Q, int64_t ldq, int width, const int32_t* d_rows,
+                      const int32_t* d_items, int64_t n, float* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -375,6 +375,23 @@ class ConvncfStepArgs(C.Structure):
          ("reg_net", C.c_float)]
 
 
+CFGAN_MAX_HIDDEN = 3
+
+
+class CfganNet(C.Structure):
+    """nrhip_cfgan_net (include/neurec_hip.h)"""
+    _fields_ = [(n, C.c_void_p * (CFGAN_MAX_HIDDEN + 1)) for n in ("W", "b", "G_W", "G_b", "m_W", "m_b", "v_W", "v_b")] + \
+        [("n_hidden", C.c_int), ("width", C.c_int * CFGAN_MAX_HIDDEN)]
+
+
+class CfganStepArgs(C.Structure):
+    """nrhip_cfgan_step_args (include/neurec_hip.h)"""
+    _fields_ = [("gen", CfganNet), ("dis", CfganNet)] + \
+        [(n, C.c_void_p) for n in ("indptr", "indices", "rows", "ent_ptr", "zr", "pm", "keys", "ws", "gemm_ws")] + \
+        [("gemm_ws_bytes", C.c_size_t), ("loss3", C.c_void_p)] + \
+        [(n, C.c_int) for n in ("n_rows", "n_cols", "batch", "n_ent", "max_batch")] + [("zr_coef", C.c_float)]
+
+
 DEEPICF_MAX_LAYERS = 4
 
 
@@ -637,6 +654,13 @@ SIGNATURES = {
     "nrhip_convncf_step": [C.POINTER(ConvncfStepArgs), p],
     "nrhip_convncf_pairs": [C.POINTER(ConvncfWeights), p, p, i32, p, p],
     "nrhip_convncf_scores": [C.POINTER(ConvncfWeights), p, i32, p, i64, p],
+    "nrhip_cfgan_workspace": [C.POINTER(CfganStepArgs), psz, psz],
+    "nrhip_cfgan_masks": [p, p, p, p, i32, i32, i32, u64, u64, p, p, p],
+    "nrhip_cfgan_d_step": [C.POINTER(CfganStepArgs), p],
+    "nrhip_cfgan_g_step": [C.POINTER(CfganStepArgs), p],
+    "nrhip_cfgan_apply": [C.POINTER(CfganNet), i32, i32, i32, f32, f32, f32, f32, f32, p, p, p],
+    "nrhip_cfgan_hidden": [C.POINTER(CfganNet), p, p, p, i32, i32, p, p, i64, p],
+    "nrhip_cfgan_pairs": [p, i64, p, i64, i32, p, p, i64, p, p],
 }
 
 for _name, _args in SIGNATURES.items():

@@ -85,6 +85,10 @@ MODELS = {
                 ("net_channel", "[32,32,32,32,32,32]"), ("lr_embed", "0.05"), ("lr_net", "0.05"),
                 ("num_negatives", "4"), ("loss_function", "BPR"), ("keep", "1.0"), ("embed_init_method", "tnormal"),
                 ("weight_init_method", "xavier_normal"), ("stddev", "0.01"), ("verbose", "1")],
+    "CFGAN": [("reg_G", "0.001"), ("reg_D", "0.0"), ("lr_G", "0.0001"), ("lr_D", "0.0001"), ("ZR_ratio", "0.7"),
+              ("ZP_ratio", "0.7"), ("ZR_coefficient", "0.03"), ("hiddenLayer_G", "[400]"), ("hiddenLayer_D", "[125]"),
+              ("batchSize_G", "32"), ("batchSize_D", "64"), ("step_G", "1"), ("step_D", "1"), ("mode", "userBased"),
+              ("opt_G", "adam"), ("opt_D", "adam"), ("epochs", "100"), ("verbose", "1")],
 }
 
 
