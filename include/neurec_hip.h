@@ -2585,6 +2585,51 @@ int nrhip_cfgan_hidden(const nrhip_cfgan_net* net, const int64_t* d_indptr, cons
 int nrhip_cfgan_pairs(const float* d_F, int64_t ldf, const float* d_Q, int64_t ldq, int width, const int32_t* d_rows,
                       const int32_t* d_items, int64_t n, float* d_out, void* stream);
 
+/* ---- IRGAN (two matrix-factorisation triples in a minimax game; the generator samples from its own softmax) --------
+ * These symbols are additions: no existing struct changes and NRHIP_ABI_VERSION stays 4.
+ * Two triples (P [n_users][d], Q [n_items][d], b [n_items]): G and D, plain gradient descent with one lr.
+ * Weights of a row of logits z at temperature tau: w_i = floor(exp((z_i - max z) / tau) 2^31) as uint32, W = sum w_i in
+ * 64 bits.  A draw is a pure function of (seed, pass, phase, user, draw index) through nr::XorShift64s seeded with
+ * (seed, ((pass << 2 | phase) << 32) | user, draw index), three words h0, h1, h2:
+ *     phase 0 (D data, IRGAN.py:175-193): the smallest i whose inclusive prefix sum exceeds mulhi64(h0, W)
+ *     phase 1 (G step, IRGAN.py:220-224): mulhi64(h0, 5) == 0 ? the positive at index mulhi64(h1, deg)
+ *                                                              : the smallest i whose prefix sum exceeds mulhi64(h2, W) */
+#define NRHIP_IRGAN_MAX_D 128
+#define NRHIP_IRGAN_MAX_BATCH 1024
+typedef struct nrhip_irgan_args {
+  float* d_Pg; float* d_Qg; float* d_bg;          /* the generator */
+  float* d_Pd; float* d_Qd; float* d_bd;          /* the discriminator */
+  const int64_t* d_indptr;                        /* the train CSR, [n_users + 1] */
+  const int32_t* d_indices;                       /* ascending per row */
+  float* d_z;                                     /* [n_items]: the logits of the last G step's user */
+  uint32_t* d_w;                                  /* [n_items]: the weights its draws were made from */
+  int32_t* d_draw_items;                          /* [2][2 max_deg]: the draws as made, then sorted by (item, index) */
+  float* d_draw_r;                                /* [2][2 max_deg]: their rewards times p / pn, same two orders */
+  float* d_hdr;                                   /* [4]: max z, sum exp(z - max), R, S (an int) */
+  float* d_ws; size_t ws_floats;                  /* nrhip_irgan_workspace */
+  int n_users, n_items, d, max_deg, max_batch;
+  float lr, g_reg, d_reg;
+  uint64_t seed;
+} nrhip_irgan_args;
+int nrhip_irgan_workspace(int n_items, int d, int max_batch, size_t* floats);
+/* d_z [rows][ld] logits -> the uint32 weights of each row over its first n entries, IN PLACE */
+int nrhip_irgan_weights(float* d_z, int64_t ld, int rows, int n, double tau, void* stream);
+/* row r of d_w belongs to user d_users[r].  phase 0: deg(u) draws; the interleaved (u, pos_k, 1), (u, draw_k, 0) go to
+ * d_out_*[d_out_off[r] + 2 k (+ 1)].  phase 1: 2 deg(u) mixture draws to d_out_items[d_out_off[r] + k] */
+int nrhip_irgan_draws(const uint32_t* d_w, int64_t ld, int rows, int n, const int32_t* d_users, const int64_t* d_indptr,
+                      const int32_t* d_indices, const int64_t* d_out_off, int phase, uint64_t seed, uint64_t pass,
+                      int32_t* d_out_users, int32_t* d_out_items, float* d_out_labels, void* stream);
+/* Replaces the `sess.run(self.discriminator.d_updates, ...)` loop of IRGAN.py:207-211: ceil(n / batch) steps over the
+ * triples d_users / d_items / d_labels [>= n] taken in the order d_order [n] (NULL: as they lie), the last step short.
+ * d_loss (or NULL) [steps][3]: sum of the cross entropies, B d_reg / 2 (sum |P_u|^2 + sum |Q_i|^2), B d_reg / 2 sum
+ * b_i^2 over the occurrences, all from before the step. */
+int nrhip_irgan_d_pass(const nrhip_irgan_args* args, const int32_t* d_users, const int32_t* d_items,
+                       const float* d_labels, const int32_t* d_order, int64_t n, int batch, float* d_loss, void* stream);
+/* Replaces the loop of IRGAN.py:214-235 over h_users (a HOST array), one user step after the other: four launches per
+ * user.  d_given (or NULL; one user only): 2 deg(u) recorded draws in place of made ones. */
+int nrhip_irgan_g_pass(const nrhip_irgan_args* args, const int32_t* h_users, int n_users, const int32_t* d_given,
+                       uint64_t pass, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -392,6 +392,14 @@ class CfganStepArgs(C.Structure):
         [(n, C.c_int) for n in ("n_rows", "n_cols", "batch", "n_ent", "max_batch")] + [("zr_coef", C.c_float)]
 
 
+class IrganArgs(C.Structure):
+    """nrhip_irgan_args (include/neurec_hip.h)"""
+    _fields_ = [(n, C.c_void_p) for n in ("Pg", "Qg", "bg", "Pd", "Qd", "bd", "indptr", "indices", "z", "w", "draw_items",
+                                          "draw_r", "hdr", "ws")] + [("ws_floats", C.c_size_t)] + \
+        [(n, C.c_int) for n in ("n_users", "n_items", "d", "max_deg", "max_batch")] + \
+        [(n, C.c_float) for n in ("lr", "g_reg", "d_reg")] + [("seed", C.c_uint64)]
+
+
 DEEPICF_MAX_LAYERS = 4
 
 
@@ -661,6 +669,11 @@ SIGNATURES = {
     "nrhip_cfgan_apply": [C.POINTER(CfganNet), i32, i32, i32, f32, f32, f32, f32, f32, p, p, p],
     "nrhip_cfgan_hidden": [C.POINTER(CfganNet), p, p, p, i32, i32, p, p, i64, p],
     "nrhip_cfgan_pairs": [p, i64, p, i64, i32, p, p, i64, p, p],
+    "nrhip_irgan_workspace": [i32, i32, i32, psz],
+    "nrhip_irgan_weights": [p, i64, i32, i32, C.c_double, p],
+    "nrhip_irgan_draws": [p, i64, i32, i32, p, p, p, p, i32, u64, u64, p, p, p, p],
+    "nrhip_irgan_d_pass": [C.POINTER(IrganArgs), p, p, p, p, i64, i32, p, p],
+    "nrhip_irgan_g_pass": [C.POINTER(IrganArgs), p, i32, p, u64, p],
 }
 
 for _name, _args in SIGNATURES.items():

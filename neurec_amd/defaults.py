@@ -89,6 +89,9 @@ MODELS = {
               ("ZP_ratio", "0.7"), ("ZR_coefficient", "0.03"), ("hiddenLayer_G", "[400]"), ("hiddenLayer_D", "[125]"),
               ("batchSize_G", "32"), ("batchSize_D", "64"), ("step_G", "1"), ("step_D", "1"), ("mode", "userBased"),
               ("opt_G", "adam"), ("opt_D", "adam"), ("epochs", "100"), ("verbose", "1")],
+    "IRGAN": [("lr", "0.001"), ("factors_num", "20"), ("batch_size", "32"), ("epochs", "10"), ("d_epoch", "1"),
+              ("g_epoch", "1"), ("g_reg", "0.0"), ("d_reg", "0.1/16"), ("d_tau", "0.2"),
+              ("pretrain_file", "dataset/ml100k_saved_model.pkl")],
 }
 
 
