@@ -2630,6 +2630,110 @@ int nrhip_irgan_d_pass(const nrhip_irgan_args* args, const int32_t* d_users, con
 int nrhip_irgan_g_pass(const nrhip_irgan_args* args, const int32_t* h_users, int n_users, const int32_t* d_given,
                        uint64_t pass, void* stream);
 
+/* ---- SBPR (social BPR: a third, social item per positive; Zhao et al., CIKM 2014) ---------------------------------
+ * These symbols are additions: no existing struct changes and NRHIP_ABI_VERSION stays 4.
+ * Replaces model/social_recommender/SBPR.py: _get_SocialItemsSet (:40-49), _get_pairwise_all_data with the
+ * DataIterator's permutation (:104-106, 122-148) and `sess.run((self.loss, self.optimizer), feed_dict)` (:115).
+ * CSR inputs: int64 indptr [n_users + 1], int32 indices ascending per row; the trust CSR deduplicated.
+ *
+ * Social sets.  C_u = the distinct items k that some user f trusted by u has in their train row and u has not, with
+ * count(u, k) = the number of such f (= suk - 1); users without train items have no set, trusted users without train
+ * items add nothing.  nrhip_sbpr_expansion_sizes: d_sizes [n_users] = sum over f in S_u of |R_f| (0 for a user without
+ * train items).  nrhip_sbpr_sets_block: the sets of the users [u0, u1), whose expansions lie one after the other at
+ * d_pair_off [u1 - u0 + 1] (exclusive offsets, the last = n_pairs <= NRHIP_SBPR_MAX_PAIRS).  Output: d_indptr_out
+ * [u1 - u0 + 1] offsets into d_items_out / d_counts_out [>= n_pairs] (items ascending per user), *d_total the number of
+ * entries.  Work buffers: d_keys uint64 [n_pairs], d_cnt and d_pos int32 [n_pairs], d_chunk int64
+ * [ceil(n_pairs / 1024) + 1].  The sort: a user's keys lie together, so with d_seg_len (the length of each user's
+ * expansion, 0 for one above max_seg_len <= NRHIP_SBPR_SEGMENT_PAIRS) the users' segments are sorted on their own in
+ * one launch, and the n_big larger ones, listed in the HOST arrays h_big_off / h_big_len, by one nrhip_sort_u64 each;
+ * d_seg_len NULL: one sort of the whole block.  No atomics: the same result on every run. */
+#define NRHIP_SBPR_SEGMENT_PAIRS 16384
+#define NRHIP_SBPR_MAX_PAIRS (1ll << 30)
+#define NRHIP_SBPR_MAX_D 128
+#define NRHIP_SBPR_MAX_BATCH (1 << 24)
+typedef struct nrhip_sbpr_sets_args {
+  const int64_t* d_tr_indptr;
+  const int32_t* d_tr_indices;
+  const int64_t* d_s_indptr;
+  const int32_t* d_s_indices;
+  const int64_t* d_pair_off;
+  uint64_t* d_keys;
+  int32_t* d_cnt;
+  int32_t* d_pos;
+  int64_t* d_chunk;
+  int32_t* d_items_out;
+  int32_t* d_counts_out;
+  int64_t* d_indptr_out;
+  int64_t* d_total;
+  const int32_t* d_seg_len;       /* [u1 - u0] or NULL: see above */
+  const int64_t* h_big_off;       /* HOST arrays [n_big] */
+  const int64_t* h_big_len;
+  int n_users, n_items, u0, u1;
+  int64_t n_pairs;
+  int max_seg_len, n_big;
+} nrhip_sbpr_sets_args;
+int nrhip_sbpr_expansion_sizes(const int64_t* d_tr_indptr, const int64_t* d_s_indptr, const int32_t* d_s_indices,
+                               int n_users, int64_t* d_sizes, void* stream);
+int nrhip_sbpr_sets_block(const nrhip_sbpr_sets_args* args, void* stream);
+/* One epoch's instances.  Slots: one per (eligible user, train item), eligible users d_elig [n_elig] ascending, slot s of
+ * row r = d_slot_row[s] is train item s - d_slot_ptr[r] of user d_elig[r].  Output position p in [out_begin, out_begin +
+ * out_count) carries slot perm(p) (shuffle != 0; the keyed bijection of nrhip_sample_instances_epoch) and writes entry
+ * p - out_begin of the five outputs (u, i, k, j, suk).  The draws are a pure function of (seed, epoch, slot) through
+ * nr::XorShift64s seeded with them: word 0, h: k = C_u[mulhi64(h, |C_u|)] and suk = count(u, k) + 1; words 1.. are the
+ * attempts at j = mulhi64(h, n_items), rejected while j is in R_u or C_u; after 64 rejections j is the r-th id outside
+ * both, r = mulhi64(next word, the number of such ids).  j = -1 when no id is outside both. */
+typedef struct nrhip_sbpr_stream_args {
+  const int64_t* d_tr_indptr;
+  const int32_t* d_tr_indices;
+  const int64_t* d_c_indptr;      /* [n_users + 1] */
+  const int32_t* d_c_items;
+  const int32_t* d_c_counts;
+  const int64_t* d_slot_ptr;      /* [n_elig + 1] */
+  const int32_t* d_slot_row;      /* [n_slots] */
+  const int32_t* d_elig;          /* [n_elig] */
+  int32_t* d_users_out;
+  int32_t* d_items_out;
+  int32_t* d_social_out;
+  int32_t* d_neg_out;
+  float* d_suk_out;
+  int64_t n_slots, out_begin, out_count;
+  uint64_t seed, epoch;
+  int n_elig, n_users, n_items, shuffle;
+} nrhip_sbpr_stream_args;
+int nrhip_sbpr_stream(const nrhip_sbpr_stream_args* args, void* stream);
+/* The step on slots (u, i, k, j, suk), P [n_users][d], Q [n_items][d], b [n_items]:
+ *     x_a = P[u] . Q[a] + b[a];   y1 = (x_i - x_k) / suk,   y2 = x_k - x_j
+ *     loss = pairwise_loss(kind, y1) + pairwise_loss(kind, y2) + reg l2_loss(P[u], Q[k], Q[i], Q[j], b[i], b[k], b[j])
+ * with l2_loss = sum(x^2) / 2 per occurrence and the loss kinds of nrhip_pairwise_mf_grad.  i, k and j may coincide
+ * within a slot and across slots.  Output: d_loss2 = (loss term, regulariser term) of the tables as they come in; the
+ * rows of d_G_P / d_G_Q / d_G_b the batch looked up are STORED (the others are left alone: keep them zero), each the
+ * sum over its occurrences in the order of the sorted keys: by slot, in one slot i before k before j.  d_flag_* (uint8
+ * per row, may be NULL) are set for the rows nrhip_optimizer_rows_tf is to move.  A slot with an id that is no table
+ * row takes no part.  Work buffers: d_keys uint64 [4 batch], d_scal float [4 batch].  batch == 0 launches nothing.
+ * d = 1..NRHIP_SBPR_MAX_D.  Every sum is taken in a fixed order: two calls on the same inputs are bit-identical. */
+typedef struct nrhip_sbpr_step_args {
+  const float* d_P;
+  const float* d_Q;
+  const float* d_b;
+  float* d_G_P;
+  float* d_G_Q;
+  float* d_G_b;
+  uint8_t* d_flag_P;
+  uint8_t* d_flag_Q;
+  uint8_t* d_flag_b;
+  const int32_t* d_users;
+  const int32_t* d_items;
+  const int32_t* d_social;
+  const int32_t* d_neg;
+  const float* d_suk;
+  uint64_t* d_keys;
+  float* d_scal;
+  float* d_loss2;
+  int n_users, n_items, d, batch, loss_kind;
+  float reg;
+} nrhip_sbpr_step_args;
+int nrhip_sbpr_step(const nrhip_sbpr_step_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

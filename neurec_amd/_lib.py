@@ -226,6 +226,33 @@ class TransrecStepArgs(C.Structure):
         [(n, C.c_int) for n in ("n_users", "n_items", "d", "batch", "pairwise", "loss_kind")] + [("reg", C.c_float)]
 
 
+class SbprSetsArgs(C.Structure):
+    """nrhip_sbpr_sets_args (include/neurec_hip.h)"""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "tr_indptr", "tr_indices", "s_indptr", "s_indices", "pair_off", "keys", "cnt", "pos", "chunk", "items_out",
+        "counts_out", "indptr_out", "total", "seg_len", "big_off", "big_len")] + \
+        [(n, C.c_int) for n in ("n_users", "n_items", "u0", "u1")] + [("n_pairs", C.c_int64)] + \
+        [(n, C.c_int) for n in ("max_seg_len", "n_big")]
+
+
+class SbprStreamArgs(C.Structure):
+    """nrhip_sbpr_stream_args (include/neurec_hip.h)"""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "tr_indptr", "tr_indices", "c_indptr", "c_items", "c_counts", "slot_ptr", "slot_row", "elig", "users_out",
+        "items_out", "social_out", "neg_out", "suk_out")] + \
+        [(n, C.c_int64) for n in ("n_slots", "out_begin", "out_count")] + \
+        [(n, C.c_uint64) for n in ("seed", "epoch")] + \
+        [(n, C.c_int) for n in ("n_elig", "n_users", "n_items", "shuffle")]
+
+
+class SbprStepArgs(C.Structure):
+    """nrhip_sbpr_step_args (include/neurec_hip.h)"""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "P", "Q", "b", "G_P", "G_Q", "G_b", "flag_P", "flag_Q", "flag_b", "users", "items", "social", "neg", "suk",
+        "keys", "scal", "loss2")] + \
+        [(n, C.c_int) for n in ("n_users", "n_items", "d", "batch", "loss_kind")] + [("reg", C.c_float)]
+
+
 GRU4REC_MAX_LAYERS = 3
 
 
@@ -674,6 +701,10 @@ SIGNATURES = {
     "nrhip_irgan_draws": [p, i64, i32, i32, p, p, p, p, i32, u64, u64, p, p, p, p],
     "nrhip_irgan_d_pass": [C.POINTER(IrganArgs), p, p, p, p, i64, i32, p, p],
     "nrhip_irgan_g_pass": [C.POINTER(IrganArgs), p, i32, p, u64, p],
+    "nrhip_sbpr_expansion_sizes": [p, p, p, i32, p, p],
+    "nrhip_sbpr_sets_block": [C.POINTER(SbprSetsArgs), p],
+    "nrhip_sbpr_stream": [C.POINTER(SbprStreamArgs), p],
+    "nrhip_sbpr_step": [C.POINTER(SbprStepArgs), p],
 }
 
 for _name, _args in SIGNATURES.items():

@@ -92,6 +92,9 @@ MODELS = {
     "IRGAN": [("lr", "0.001"), ("factors_num", "20"), ("batch_size", "32"), ("epochs", "10"), ("d_epoch", "1"),
               ("g_epoch", "1"), ("g_reg", "0.0"), ("d_reg", "0.1/16"), ("d_tau", "0.2"),
               ("pretrain_file", "dataset/ml100k_saved_model.pkl")],
+    "SBPR": [("learning_rate", "0.001"), ("embedding_size", "16"), ("learner", "adam"), ("loss_function", "bpr"),
+             ("num_epochs", "500"), ("reg_mf", "0.01"), ("batch_size", "512"), ("social_file", "dataset/Ciao_u5_s2.uu"),
+             ("init_method", "normal"), ("stddev", "0.01"), ("verbose", "1")],
 }
 
 

@@ -59,3 +59,29 @@ class SeqAbstractRecommender(AbstractRecommender):
         if dataset.time_matrix is None:
             raise ValueError("Dataset does not contant time infomation!")
         super(SeqAbstractRecommender, self).__init__(dataset, conf)
+
+
+def read_trust_lines(path, sep, userids):
+    """the (user row, friend row) pairs of a trust file with two columns, in file order: lines whose user or friend is
+    no key of `userids` are dropped (AbstractRecommender.py:58-70).  Deviation, on purpose: the file's columns and the
+    keys are compared in their STRING form — the reference's np.in1d keeps nothing when the file parses as integers
+    and the keys are strings (or the other way round)"""
+    import pandas as pd
+    lines = pd.read_csv(path, sep=sep, header=None, names=["user", "friend"], dtype=str, skipinitialspace=True)
+    by_text = {str(k).strip(): int(v) for k, v in userids.items()}
+    user = lines["user"].astype(str).str.strip().map(by_text)
+    friend = lines["friend"].astype(str).str.strip().map(by_text)
+    keep = user.notna() & friend.notna()
+    return user[keep].astype("int64").to_numpy(), friend[keep].astype("int64").to_numpy()
+
+
+class SocialAbstractRecommender(AbstractRecommender):
+    """base of `model/social_recommender/` (AbstractRecommender.py:55-73): `social_matrix` [U, U], the directed trust
+    matrix of conf["social_file"] as given — row = the user, column = the user they trust; duplicate lines collapse to
+    one index"""
+    def __init__(self, dataset, conf):
+        import scipy.sparse as sp
+        super(SocialAbstractRecommender, self).__init__(dataset, conf)
+        user_id, friend_id = read_trust_lines(conf["social_file"], conf["data.convert.separator"], dataset.userids)
+        num_users, num_items = dataset.train_matrix.shape
+        self.social_matrix = sp.csr_matrix(([1] * len(user_id), (user_id, friend_id)), shape=(num_users, num_users))

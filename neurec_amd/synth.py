@@ -212,3 +212,25 @@ def device_test_rows(train_rows, n_items, per_user=2, seed=2019):
     if idx.numel() == 0:
         idx = torch.zeros(1, dtype=torch.int32, device=dev)
     return E.DeviceCSR(indptr, idx, n_items)
+
+
+def trust_graph(n_users, seed=2019, mean_log_degree=1.2, sigma=0.8, every_empty=11, has_items=None):
+    """A directed trust graph over n_users as a CSR matrix [U, U] (row = the user, columns = the users they trust):
+    out-degree round(LogNormal(mean_log_degree, sigma)), every `every_empty`-th user trusts nobody, the trusted users
+    drawn with a power-law popularity (a few users are trusted by many) among the users `has_items` marks (None:
+    everyone).  Duplicates collapse; a user may trust themself."""
+    rng = np.random.RandomState(seed)
+    pool = np.arange(n_users) if has_items is None else np.flatnonzero(np.asarray(has_items))
+    deg = np.round(rng.lognormal(mean_log_degree, sigma, n_users)).astype(np.int64)
+    deg[::every_empty] = 0
+    deg = np.minimum(deg, len(pool))
+    pop = (np.arange(len(pool)) + 10.0) ** -0.8
+    rng.shuffle(pop)
+    cdf = np.cumsum(pop / pop.sum())
+    owner = np.repeat(np.arange(n_users, dtype=np.int64), deg)
+    friend = pool[np.minimum(np.searchsorted(cdf, rng.random_sample(owner.shape[0])), len(pool) - 1)]
+    S = sp.csr_matrix((np.ones(len(owner), np.float32), (owner, friend)), shape=(n_users, n_users))
+    S.sum_duplicates()
+    S.sort_indices()
+    S.data[:] = 1.0
+    return S
