@@ -2734,6 +2734,90 @@ typedef struct nrhip_sbpr_step_args {
 } nrhip_sbpr_step_args;
 int nrhip_sbpr_step(const nrhip_sbpr_step_args* args, void* stream);
 
+/* ---- JCA (joint collaborative autoencoders on a block of the rating matrix; Zhu et al., WWW 2019) -----------------
+ *
+ * Replaces model/general_recommender/JCA.py.  A block is n_rows batch users d_rows and n_cols batch items d_cols (each
+ * distinct, at most batch_size <= NRHIP_JCA_MAX_BATCH), H = hidden_neuron <= NRHIP_JCA_MAX_H:
+ *     hu[a]  = g(sum over i in R[r_a,:] of UV[i,:] + Ub1)                              [n_rows, H]
+ *     hi[b]  = g((sum over u in R[:,c_b] of IV[u,:] + Ib1) * IF[c_b])                  [n_cols, H]
+ *     D[a,b] = (f(hu[a] . UW[:,c_b] + Ub2[c_b]) + f(hi[b] . IW[:,r_a] + Ib2[r_a])) / 2
+ *     cost   = sum over pairs (a, bp, bn) of max(0, D[a,bn] - D[a,bp] + margin) + reg * 0.5 * sum over the eight
+ *              tables of sum(w^2) / 2      (IF = I_factor_vector is not regularised)
+ * Every variable, its two optimiser slots and its gradient live at the same offsets of four flat float arrays d_W, d_M,
+ * d_V and d_G, in this order: UV [I][H], UWt [I][H] (UW transposed), IV [U][H], IWt [U][H] (IW transposed), Ub2 [I],
+ * IF [I], Ib2 [U], Ub1 [H], Ib1 [H]: 2 (U + I) H + 2 I + U + 2 H floats.  d_flag (uint8 [4 I + 3 U]): the touched rows
+ * of UV, UWt, IV, IWt, then of Ub2, IF, Ib2.  d_indptr / d_indices: the train CSR; d_t_indptr / d_t_users: its transpose
+ * (users ascending per item).  d_rowslot int64 [U] and d_colslot int64 [I] (zero at first) map a batch row or column to
+ * its position under `stamp`, which the caller raises by one per call (>= 1).  nrhip_jca_workspace fills out[4]: the
+ * floats of d_wsf, the int32 of d_wsi, the doubles of d_wsd and the uint32 of d_pairs for (U, I, H, batch_size, num_neg).
+ * The ids of d_rows / d_cols / users / items are the caller's to check: they index tables.
+ *
+ * nrhip_jca_pairs: the block's observed bit set (n_rows x n_cols bits, built in LDS a row per wavefront) and the pair
+ * list, row-major over the stored entries of the block, num_neg pairs each, one uint32 a << 18 | bp << 9 | bn per pair;
+ * *d_total = the number of pairs.  A block row with fewer than num_neg unobserved columns gives no pair.  Negative k of
+ * the positive at (a, bp) is a pure function of (seed, epoch, block_i, block_j, a * 512 + bp, k, attempt): the
+ * generator nr::XorShift64s seeded (seed ^ splitmix64(block_i << 32 | block_j), epoch, (a * 512 + bp) * 8 + k); each
+ * attempt is mulhi64(next(), n_cols), rejected if observed or taken by an earlier k; after 64 rejections the
+ * mulhi64(next(), free)-th free column in ascending order.
+ *
+ * nrhip_jca_step: the gradients of one block from n_pairs pairs (nrhip_jca_pairs' or the caller's): d_loss2[0] = the
+ * hinge term; the touched rows of d_G are STORED and flagged (the rest of d_G must be zero).  dD is an integer count
+ * per cell summed with integer atomics, every float sum is taken in a fixed order: reruns are bit-identical.  A pair is
+ * active when D[a,bn] - D[a,bp] + margin > 0.
+ *
+ * nrhip_jca_apply: one sweep over all nine variables: g + 0.5 reg w on the eight tables, then Adam (adam != 0:
+ * `step` = lr_t, TensorFlow's form with epsilon outside the root) or gradient descent (`step` = lr).  A gradient is
+ * read only under its flag; d_G and d_flag are zero afterwards.  Under gd with reg == 0 only flagged rows are visited.
+ * d_loss2[1] = reg * 0.5 * sum(w^2) / 2 of the variables as they come in (0 when reg == 0).
+ *
+ * nrhip_jca_encode: which = 0: d_out [n][H] = hu of the users d_ids (NULL: 0..n-1); which = 1: hi of the items.
+ * nrhip_jca_score: d_out [n][ld] = D of the users d_users (hu d_hu [n][H]) against every item (d_hi [I][H]).
+ * nrhip_jca_score_pairs: d_out [n] = D of (d_users[p], d_items[p]) with hu row d_slot[p] of d_hu. */
+#define NRHIP_JCA_MAX_H 128
+#define NRHIP_JCA_MAX_BATCH 512
+#define NRHIP_JCA_MAX_NEG 8
+#define NRHIP_JCA_ACT_SIGMOID 0
+#define NRHIP_JCA_ACT_TANH 1
+#define NRHIP_JCA_ACT_RELU 2
+#define NRHIP_JCA_ACT_ELU 3
+#define NRHIP_JCA_ACT_IDENTITY 4
+typedef struct nrhip_jca_args {
+  float* d_W;
+  float* d_M;
+  float* d_V;
+  float* d_G;
+  uint8_t* d_flag;
+  const int64_t* d_indptr;
+  const int32_t* d_indices;
+  const int64_t* d_t_indptr;
+  const int32_t* d_t_users;
+  int64_t* d_rowslot;
+  int64_t* d_colslot;
+  float* d_wsf;
+  int32_t* d_wsi;
+  double* d_wsd;
+  const int32_t* d_rows;
+  const int32_t* d_cols;
+  uint32_t* d_pairs;
+  int32_t* d_total;
+  float* d_loss2;
+  int64_t n_pairs, stamp;
+  uint64_t seed, epoch;
+  int n_users, n_items, H, batch_size, num_neg, n_rows, n_cols, f_act, g_act, block_i, block_j;
+  float margin, reg;
+} nrhip_jca_args;
+int nrhip_jca_workspace(int n_users, int n_items, int H, int batch_size, int num_neg, int64_t* out);
+int nrhip_jca_pairs(const nrhip_jca_args* args, void* stream);
+int nrhip_jca_step(const nrhip_jca_args* args, void* stream);
+int nrhip_jca_apply(const nrhip_jca_args* args, int adam, float step, float beta1, float beta2, float eps,
+                    void* stream);
+int nrhip_jca_encode(const nrhip_jca_args* args, int which, const int32_t* d_ids, int n, float* d_out, void* stream);
+int nrhip_jca_score(const nrhip_jca_args* args, const int32_t* d_users, int n, const float* d_hu, const float* d_hi,
+                    float* d_out, int64_t ld, void* stream);
+int nrhip_jca_score_pairs(const nrhip_jca_args* args, const int32_t* d_users, const int32_t* d_items,
+                          const int32_t* d_slot, int64_t n, const float* d_hu, const float* d_hi, float* d_out,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -253,6 +253,16 @@ class SbprStepArgs(C.Structure):
         [(n, C.c_int) for n in ("n_users", "n_items", "d", "batch", "loss_kind")] + [("reg", C.c_float)]
 
 
+class JcaArgs(C.Structure):
+    """nrhip_jca_args (include/neurec_hip.h)"""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "W", "M", "V", "G", "flag", "indptr", "indices", "t_indptr", "t_users", "rowslot", "colslot", "wsf", "wsi",
+        "wsd", "rows", "cols", "pairs", "total", "loss2")] + \
+        [("n_pairs", C.c_int64), ("stamp", C.c_int64), ("seed", C.c_uint64), ("epoch", C.c_uint64)] + \
+        [(n, C.c_int) for n in ("n_users", "n_items", "H", "batch_size", "num_neg", "n_rows", "n_cols", "f_act",
+                                "g_act", "block_i", "block_j")] + [("margin", C.c_float), ("reg", C.c_float)]
+
+
 GRU4REC_MAX_LAYERS = 3
 
 
@@ -705,6 +715,13 @@ SIGNATURES = {
     "nrhip_sbpr_sets_block": [C.POINTER(SbprSetsArgs), p],
     "nrhip_sbpr_stream": [C.POINTER(SbprStreamArgs), p],
     "nrhip_sbpr_step": [C.POINTER(SbprStepArgs), p],
+    "nrhip_jca_workspace": [i32, i32, i32, i32, i32, p],
+    "nrhip_jca_pairs": [C.POINTER(JcaArgs), p],
+    "nrhip_jca_step": [C.POINTER(JcaArgs), p],
+    "nrhip_jca_apply": [C.POINTER(JcaArgs), i32, C.c_float, C.c_float, C.c_float, C.c_float, p],
+    "nrhip_jca_encode": [C.POINTER(JcaArgs), i32, p, i32, p, p],
+    "nrhip_jca_score": [C.POINTER(JcaArgs), p, i32, p, p, p, i64, p],
+    "nrhip_jca_score_pairs": [C.POINTER(JcaArgs), p, p, p, i64, p, p, p, p],
 }
 
 for _name, _args in SIGNATURES.items():

@@ -95,6 +95,9 @@ MODELS = {
     "SBPR": [("learning_rate", "0.001"), ("embedding_size", "16"), ("learner", "adam"), ("loss_function", "bpr"),
              ("num_epochs", "500"), ("reg_mf", "0.01"), ("batch_size", "512"), ("social_file", "dataset/Ciao_u5_s2.uu"),
              ("init_method", "normal"), ("stddev", "0.01"), ("verbose", "1")],
+    "JCA": [("hidden_neuron", "50"), ("epochs", "200"), ("f_act", "tanh"), ("g_act", "tanh"), ("batch_size", "256"),
+            ("reg", "0"), ("learning_rate", "0.001"), ("corruption_level", "0.2"), ("learner", "adam"),
+            ("margin", "0.15"), ("num_neg", "1"), ("init_method", "tnormal"), ("stddev", "0.01"), ("verbose", "1")],
 }
 
 
