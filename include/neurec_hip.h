@@ -436,7 +436,11 @@ int nrhip_spmm_csr(const void* plan, const int64_t* d_indptr, const int32_t* d_i
  *     rows only);
  *   d_y_row_wanted[r] == 0 says output row r is not needed: it is left untouched (last
  *     forward hop of a training step: the loss reads E* on the batch rows only).
- * Produced rows are bit-identical to nrhip_spmm_csr's. */
+ * Produced rows are bit-identical to nrhip_spmm_csr's, with one exception: behind a lane-group schedule with
+ * column blocks (block_bytes > 0: several phases) the d = 64 row-masked hop walks its own schedule, which cuts a
+ * row of more than seg_len non-zeros into seg_len-long segments by position, while the full pass cuts it per column
+ * block — such a row's partial sums are then added in another association (rows of <= seg_len non-zeros keep every
+ * bit; engine.SpmmCSR never asks for column blocks). */
 int nrhip_spmm_csr_masked(const void* plan, const int64_t* d_indptr, const int32_t* d_indices,
                           const float* d_vals, const float* d_X, const uint8_t* d_x_row_nonzero,
                           const uint8_t* d_y_row_wanted, int d, float* d_Y, const float* d_addend,
