@@ -2822,6 +2822,62 @@ int nrhip_jca_score_pairs(const nrhip_jca_args* args, const int32_t* d_users, co
                           const int32_t* d_slot, int64_t n, const float* d_hu, const float* d_hi, float* d_out,
                           void* stream);
 
+/* ---- APR (adversarial personalized ranking: BPR-MF with a perturbation of the batch's rows inside the step) ------
+ * Replaces: APR._create_loss / _create_adversarial and the optimizer's gradients (model/general_recommender/
+ * APR.py:73-118) run as `sess.run([update_P, update_Q])` then `sess.run((loss, opt_loss, minimize(opt_loss)))`.
+ * For the triplets t = (u, i, j) over d_P [n_users][d] and d_Q [n_items][d]:
+ *     x_t = <P[u], Q[i]> - <P[u], Q[j]>     loss = sum softplus(-x_t)     s_t = -sigmoid(-x_t)           (APR.py:76-80)
+ *     Gamma_P[u] = sum_{u_t = u} s_t (Q[i_t] - Q[j_t])
+ *     Gamma_Q[r] = sum_{i_t = r} s_t P[u_t] - sum_{j_t = r} s_t P[u_t]                                   (APR.py:110)
+ * adversarial == 0:  d_G_* [row] = Gamma[row] (+ reg row, with_reg) for the batch's rows; d_loss2 = {loss, reg l2}.
+ * adversarial != 0:  Delta[row] = eps Gamma[row] / sqrt(max(|Gamma[row]|^2, 1e-12))                     (APR.py:117-118)
+ *                    (adv_random: Gamma replaced by a truncated normal of stddev 0.01, APR.py:99-104, drawn from
+ *                    (seed, step, row, column); d_delta_given [n_users + n_items][d] non-NULL: Delta read from there)
+ *     xa_t = <P[u] + Delta_P[u], Q[i] + Delta_Q[i]> - <P[u] + Delta_P[u], Q[j] + Delta_Q[j]>             (APR.py:63-71)
+ *     loss_adv = sum softplus(-xa_t)     sa_t = -reg_adv sigmoid(-xa_t)     Delta constant (stop_gradient)
+ *     d_G_P[u] = Gamma_P[u] + sum sa_t ((Q + Delta)[i_t] - (Q + Delta)[j_t]) (+ reg P[u])
+ *     d_G_Q[r] = Gamma_Q[r] + sum_{i_t = r} sa_t (P + Delta)[u_t] - sum_{j_t = r} sa_t (P + Delta)[u_t] (+ reg Q[r])
+ *     d_loss2 = {loss, reg l2 + reg_adv loss_adv}
+ * with l2 = sum(P^2) / 2 + sum(Q^2) / 2 over the WHOLE tables (APR.py:83) when with_reg != 0 and reg != 0; then every
+ * row of d_G_* outside the batch is additionally SET to reg row (the dense gradient), otherwise only the batch's rows
+ * are stored and the others must be zero.  A row's sums run over its occurrences in the order of the sort keys
+ * (row << 32 | slot * 4 + role; users, then items at n_users + item, the positive before the negative of a slot).
+ * A triplet with an id outside its table takes no part in either pass.  i == j is allowed.
+ * d_flag_* (uint8 per row, NULL for Adam): set to 1 for the batch's rows.
+ * Work buffers: d_keys uint64 [3 batch], d_scal float [4 batch] (s, softplus, sa, softplus_adv per slot), d_where
+ * int32 [3 batch] (per slot and role: the position of its row's run head), d_gamma / d_delta float [3 batch][d]
+ * (indexed by that position), d_part double [NRHIP_APR_L2_BLOCKS].
+ * n_users + n_items < 2^31 - 1; batch <= NRHIP_APR_MAX_BATCH; batch == 0 launches nothing and writes nothing (with the
+ * dense regulariser: the table sweep and the loss kernel alone);
+ * d = 1..NRHIP_APR_MAX_D (above: NRHIP_ERR_UNSUPPORTED).  fp32, the loss sums in double by a fixed tree, every sum in a
+ * fixed order, no floating-point atomics: two calls on the same inputs are bit-identical. */
+#define NRHIP_APR_MAX_D 128
+#define NRHIP_APR_MAX_BATCH (1 << 24)
+#define NRHIP_APR_L2_BLOCKS 256
+typedef struct nrhip_apr_step_args {
+  const float* d_P;
+  const float* d_Q;
+  float* d_G_P;
+  float* d_G_Q;
+  uint8_t* d_flag_P;
+  uint8_t* d_flag_Q;
+  const int32_t* d_users;
+  const int32_t* d_pos;
+  const int32_t* d_neg;
+  const float* d_delta_given;
+  uint64_t* d_keys;
+  float* d_scal;
+  int32_t* d_where;
+  float* d_gamma;
+  float* d_delta;
+  double* d_part;
+  float* d_loss2;
+  uint64_t seed, step;
+  int n_users, n_items, d, batch, adversarial, adv_random, with_reg;
+  float reg, reg_adv, eps;
+} nrhip_apr_step_args;
+int nrhip_apr_step(const nrhip_apr_step_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

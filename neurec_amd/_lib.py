@@ -263,6 +263,15 @@ class JcaArgs(C.Structure):
                                 "g_act", "block_i", "block_j")] + [("margin", C.c_float), ("reg", C.c_float)]
 
 
+class AprStepArgs(C.Structure):
+    """nrhip_apr_step_args (include/neurec_hip.h)"""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "P", "Q", "G_P", "G_Q", "flag_P", "flag_Q", "users", "pos", "neg", "delta_given", "keys", "scal", "where",
+        "gamma", "delta", "part", "loss2")] + [("seed", C.c_uint64), ("step", C.c_uint64)] + \
+        [(n, C.c_int) for n in ("n_users", "n_items", "d", "batch", "adversarial", "adv_random", "with_reg")] + \
+        [(n, C.c_float) for n in ("reg", "reg_adv", "eps")]
+
+
 GRU4REC_MAX_LAYERS = 3
 
 
@@ -722,6 +731,7 @@ SIGNATURES = {
     "nrhip_jca_encode": [C.POINTER(JcaArgs), i32, p, i32, p, p],
     "nrhip_jca_score": [C.POINTER(JcaArgs), p, i32, p, p, p, i64, p],
     "nrhip_jca_score_pairs": [C.POINTER(JcaArgs), p, p, p, i64, p, p, p, p],
+    "nrhip_apr_step": [C.POINTER(AprStepArgs), p],
 }
 
 for _name, _args in SIGNATURES.items():

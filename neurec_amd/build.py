@@ -22,7 +22,7 @@ SOURCES = ["eval_select.hip", "score_gemm.hip", "sampler.hip", "spmm.hip", "bpr.
            "step.hip", "dense.hip", "vae.hip", "spmm_blocked.hip", "route.hip", "gemm.hip", "vae_wide.hip", "ngcf_wide.hip", "vae_fused.hip",
            "score_bf16.hip", "score_i8.hip", "eval_pipeline.hip", "wrmf.hip", "itemknn.hip", "fism.hip", "nais.hip", "fpmc.hip", "fossil.hip", "hrm.hip",
            "npe.hip", "fpmcplus.hip", "transrec.hip", "gru4rec.hip", "gru4recplus.hip", "sasrec.hip", "caser.hip", "srgnn.hip",
-           "neumf.hip", "cdae.hip", "deepicf.hip", "convncf.hip", "cfgan.hip", "irgan.hip", "sbpr.hip", "jca.hip"]
+           "neumf.hip", "cdae.hip", "deepicf.hip", "convncf.hip", "cfgan.hip", "irgan.hip", "sbpr.hip", "jca.hip", "apr.hip"]
 # per-file flags.  score_i8.hip: MFMA results in the unified VGPR file instead of AGPRs — its epilogue reads every
 # accumulator of two sets per tile, and v_accvgpr_read per element doubled its VALU work (896 -> 78 reads in the loop)
 FILE_FLAGS = {"score_i8.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}

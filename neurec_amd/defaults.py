@@ -98,6 +98,9 @@ MODELS = {
     "JCA": [("hidden_neuron", "50"), ("epochs", "200"), ("f_act", "tanh"), ("g_act", "tanh"), ("batch_size", "256"),
             ("reg", "0"), ("learning_rate", "0.001"), ("corruption_level", "0.2"), ("learner", "adam"),
             ("margin", "0.15"), ("num_neg", "1"), ("init_method", "tnormal"), ("stddev", "0.01"), ("verbose", "1")],
+    "APR": [("epochs", "30"), ("batch_size", "512"), ("embedding_size", "64"), ("reg", "0"), ("reg_adv", "1"),
+            ("learning_rate", "0.001"), ("learner", "adam"), ("adv_epoch", "0"), ("adv", "grad"), ("eps", "0.5"),
+            ("adver", "1"), ("init_method", "tnormal"), ("stddev", "0.01"), ("verbose", "1")],
 }
 
 
